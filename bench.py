@@ -15,6 +15,12 @@ contiguous shard of the global packet stream — no collective on the data path
 (SURVEY.md §8(e)); gloo carries only the barrier and the max-over-ranks time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--profile udp4]
+
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds everything else the line can carry (the ideal-traffic probe, the
+scan / scatter shares, the oracle check, configs_extra, the CPU baseline and
+the host-resident rates); --dump-outputs DIR writes what the last timed step
+computed, for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -44,6 +50,7 @@ WORKLOADS = {
 NFLOWS = {"udp4": 1 << 20, "imix": 1 << 20, "vlan6_tcp": 1 << 22, "jumbo_tcp4": 1 << 24,
           "tcp4": 1 << 20, "udp4_1flow": 1, "fuzz": 1}
 SEED = 0x9E3779B97F4A7C15
+DUMP_SAMPLE = 1 << 20       # positions --dump-outputs keeps of a per-packet output
 
 
 def parse_args(argv=None):
@@ -91,7 +98,72 @@ def parse_args(argv=None):
     ap.add_argument("--dry", action="store_true",
                     help="plumbing check without a GPU (rank spawn, barrier, reductions); "
                          "prints a line marked dry, never a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also run what takes runs of its own: the "
+                         "ideal-traffic probe, the scan / scatter shares, --check, "
+                         "--extra-configs, --cpu-seconds and --pcie (all off without it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (q, hash, qidx, "
+                         "qstart; filter with --filter) as DIR/<name>.npy: whole up to "
+                         f"2^{DUMP_SAMPLE.bit_length() - 1} packets over all ranks, above that "
+                         "the same seeded sample of positions in every run")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry and args.dump_outputs:
+        ap.error("--dump-outputs needs the GPU run: --dry computes no outputs")
+    return args
+
+
+FULL_ONLY = {"cpu_seconds": 0.0, "pcie": 0, "check": 0, "extra_configs": ""}   # option: off
+
+
+def plain_run(args):
+    """Without --full only the headline is measured: every option that asks for
+    a further run is switched off.  args.ignored names those the caller set to
+    something else than off or the default (rank 0 says so on stderr)."""
+    args.ignored = []
+    if not args.full:
+        std = parse_args([])
+        for k, off in FULL_ONLY.items():
+            if getattr(args, k) not in (off, getattr(std, k)):
+                args.ignored.append("--" + k.replace("_", "-"))
+            setattr(args, k, off)
+    return args
+
+
+def dump_outputs(path, out, n: int, rank: int, world: int = 1):
+    """--dump-outputs: the arrays dispatch_dev handed back in the last timed
+    step, as float32 (q, filter: 8- and 16-bit values) or float64 (the 32-bit
+    hash, qidx and qstart), exact in both.  Per-packet arrays longer than
+    DUMP_SAMPLE // world are sampled at that many positions drawn once from SEED,
+    the same in every run and build; qstart is whole.  Rank r > 0 writes
+    <name>.rank<r>.npy, so the directory holds at most DUMP_SAMPLE positions of
+    each per-packet output (24 B a position with --filter) at any world size."""
+    import numpy as np
+    import torch
+
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    idx = None
+    keep = max(1, DUMP_SAMPLE // world)
+    if n > keep:
+        pos = np.sort(np.random.default_rng(SEED & 0xFFFFFFFF).integers(0, n, keep))
+        idx = torch.from_numpy(pos).to(out.q.device)
+    suffix = f".rank{rank}" if rank else ""
+    for name, t, unsigned, dt in (("q", out.q, False, np.float32),
+                                  ("hash", out.hash, True, np.float64),
+                                  ("qidx", out.qidx, True, np.float64),
+                                  ("qstart", out.qstart, True, np.float64),
+                                  ("filter", out.filter, False, np.float32)):
+        if t is None:
+            continue
+        if name != "qstart":
+            t = t[:n] if idx is None else t[idx]
+        a = t.cpu().numpy()
+        if unsigned:
+            a = a.view(np.uint32)
+        np.save(d / f"{name}{suffix}.npy", a.astype(dt))
 
 
 # ---- distributed plumbing (gloo: control only) -----------------------------------
@@ -867,10 +939,13 @@ def run_extra_config(eng, profile, args, world, rank, devices):
 
 def main(argv=None):
     raw = list(sys.argv[1:] if argv is None else argv)
-    args = parse_args(raw)
+    args = plain_run(parse_args(raw))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, raw)
     world, rank, local = dist_setup(args.gpus)
+    if args.ignored and rank == 0:
+        print(f"bench.py: {', '.join(args.ignored)} ignored: they act only with --full",
+              file=sys.stderr, flush=True)
     if args.dry:
         return dry_run(args, world, rank, local)
     import numpy as np
@@ -923,8 +998,10 @@ def main(argv=None):
         it[0] += 1
         eng.dispatch_dev(w_k, l_k, args.stride, n, out=o_k, compact=not args.no_compact)
 
-    probe_s = probe_traffic(batches, n, args.stride, max(args.steps, 10))
-    probe_rd_s = probe_traffic(batches, n, args.stride, max(args.steps, 10), mode=1)
+    probe_s = probe_rd_s = None
+    if args.full:
+        probe_s = probe_traffic(batches, n, args.stride, max(args.steps, 10))
+        probe_rd_s = probe_traffic(batches, n, args.stride, max(args.steps, 10), mode=1)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -944,11 +1021,13 @@ def main(argv=None):
     k_med_s = max_over_ranks(eng.timing_quantile(abi.K_PARSE_HASH) / 1e3, world) \
         if k_cnt else 0.0
     eng.timing_enable(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batches[(it[0] - 1) % nbat][2], n, rank, world)
     # the scan and scatter shares, from a separate pass after the timed one:
     # events on all three kernels widen the step by ~9 us, so the timed steps
     # carry them on the parse kernel only
     side_us = {}
-    if not args.no_compact and args.kernel_timing:
+    if args.full and not args.no_compact and args.kernel_timing:
         eng.timing_enable((1 << abi.K_SCAN) | (1 << abi.K_SCATTER))
         for _ in range(min(args.steps, 20)):
             step()
@@ -1036,6 +1115,7 @@ def main(argv=None):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",

@@ -19,6 +19,10 @@ Produces:
                       compiled from ff_dpdk_if.c:1881-1902) on the tuple
                       extracted per ff_dpdk_if.c:1994-2021, and the script
                       asserts the oracle restatement agrees.
+  ref_*.npz, ref_ini_events.json
+                      (`make_golden.py ref`, only these) what the reference's
+                      compiled code answers on the tests' seeded inputs, see
+                      ref_recorded().
 No reference source is copied: the fixtures are data (inputs and outputs).
 """
 from __future__ import annotations
@@ -168,7 +172,54 @@ def synth_fixture(profile: int):
     return out
 
 
+def ref_recorded():
+    """Answers of the reference's own compiled code (oracle/_ref) on the seeded
+    inputs of the tests that pin the oracle and the INI reader to it, so those
+    tests hold where oracle/_ref cannot be built:
+      ref_thash.npz        default key, toeplitz_hash over test_oracle.thash_cases()
+      ref_kni.npz          kni_set_bitmap over test_kni_oracle.bitmap_specs(), and
+                           get_bitmap over test_kni_oracle.lookup_cases()
+      ref_ini_events.json  ini_parse over ff_config/*.ini (the five shipped
+                           fs/config files, settings only, copied byte for
+                           byte) and over test_ffconfig.generated_inis()
+    The inputs come from the tests' own generators; only outputs are stored."""
+    import tempfile
+
+    import test_ffconfig
+    import test_kni_oracle
+    import test_oracle
+
+    R, K = oracle.ref(), oracle.ref_kni()
+    assert R is not None and K is not None, "oracle/_ref is not built"
+    key = np.array([R.ref_default_rsskey()[i] for i in range(40)], np.uint8)
+    hashes = np.array([R.ref_toeplitz_hash(kl, k, len(d), d)
+                       for kl, k, d in test_oracle.thash_cases()], np.uint32)
+    np.savez_compressed(HERE / "ref_thash.npz", key=key, hashes=hashes)
+
+    bitmaps = np.stack([oracle.ref_kni_bitmap(s) for s in test_kni_oracle.bitmap_specs()])
+    hits = np.array([bool(K.ref_get_bitmap(raw, bm.ctypes.data))
+                     for raw, bm, *_ in test_kni_oracle.lookup_cases(oracle)], np.uint8)
+    np.savez_compressed(HERE / "ref_kni.npz", bitmaps=bitmaps, hits=hits)
+
+    def rec(path):
+        ev, err = oracle.ref_ini_events(path)
+        return {"events": [list(e) for e in ev], "error": err}
+
+    out = {"configs": {p.name: rec(p) for p in sorted((HERE / "ff_config").glob("*.ini"))},
+           "generated": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        for i, data in enumerate(test_ffconfig.generated_inis()):
+            p = Path(tmp) / f"g{i}.ini"
+            p.write_bytes(data)
+            out["generated"].append(rec(p))
+    (HERE / "ref_ini_events.json").write_text(json.dumps(out, separators=(",", ":")) + "\n")
+
+
 def main():
+    if sys.argv[1:] == ["ref"]:     # only the reference's recorded answers
+        ref_recorded()
+        print("reference recordings written to", HERE)
+        return
     (HERE / "survey_kat.json").write_text(json.dumps(survey_kat(), indent=1) + "\n")
     (HERE / "thash_82599.json").write_text(json.dumps(thash_82599(), indent=1) + "\n")
     if oracle.ref() is None:

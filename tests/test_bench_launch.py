@@ -47,6 +47,24 @@ def test_gpus1_single_rank():
     assert d["n_gpus"] == 1 and len(d["config"]["devices"]) == 1
 
 
+def test_plain_run_leaves_out_the_full_legs():
+    """Without --full the options of the further legs do nothing, and the run
+    says so: no check, no CPU baseline, whatever --check and --cpu-seconds say.
+    --steps below 1 is refused, and so is --dump-outputs without the GPU run."""
+    r = _run(["--gpus", "1", "--dry", "--steps", "2", "--warmup", "0", "--pkts", "4096",
+              "--check", "4096", "--cpu-seconds", "1"])
+    assert r.returncode == 0, r.stderr
+    d = _line(r.stdout)
+    assert d["steps"] == 2 and d["check"] is None and d["cpu_baseline"] is None
+    assert "--cpu-seconds, --check ignored" in r.stderr and "--full" in r.stderr
+    r = _run(["--gpus", "1", "--dry", "--steps", "2", "--cpu-seconds", "0"])
+    assert r.returncode == 0 and "ignored" not in r.stderr      # off, or left alone: no note
+    r = _run(["--gpus", "1", "--dry", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+    r = _run(["--gpus", "1", "--dry", "--dump-outputs", "unused"])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+
+
 def test_world_size_mismatch_fails():
     r = _run(["--gpus", "2", "--dry"], {"WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0
@@ -84,8 +102,9 @@ def test_torchrun_two_ranks():
 def test_two_ranks_check_and_cpu_baseline():
     """N > 1 line: bit_exact is the AND over every rank's own shard check (a
     failing rank 1 turns it false), each rank's result is listed, and the CPU
-    baseline is present at n_gpus 2 (rank 0, after the device work)."""
-    base = ["--gpus", "2", "--dry", "--steps", "2", "--warmup", "0", "--pkts", "4096",
+    baseline is present at n_gpus 2 (rank 0, after the device work).  Both
+    belong to a --full run."""
+    base = ["--gpus", "2", "--dry", "--full", "--steps", "2", "--warmup", "0", "--pkts", "4096",
             "--check", "4096", "--cpu-seconds", "1"]
     r = _run(base, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]

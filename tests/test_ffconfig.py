@@ -1,16 +1,19 @@
 """fs/lib config ingestion on CPU.
 
 * The INI reader (yastack_amd/ffconfig.ini_parse) against the reference's own
-  parser, fs/lib/ff_ini_parser.c compiled where it lies (oracle/_ref): the five
-  shipped fs/config/*.ini files and 400 generated files with the syntax edge
-  cases inih handles (inline ';' comments, continuation lines, ':' pairs, a BOM,
-  lines past INI_MAX_LINE, broken sections), event for event and error line.
+  parser, fs/lib/ff_ini_parser.c: the five shipped fs/config/*.ini files
+  (settings only, kept byte for byte in golden/ff_config) and 400 generated files
+  with the syntax edge cases inih handles (inline ';' comments, continuation
+  lines, ':' pairs, a BOM, lines past INI_MAX_LINE, broken sections), event for
+  event and error line: against its recorded answers (golden/ref_ini_events.json)
+  and, where oracle/_ref is built, the parser compiled where it lies as well.
 * The knobs the soft-RSS path reads from those five files, against values
   derived by hand from fs/lib/ff_config.c:73-136 (nb_procs = bits of
   lcore_mask), :440-451 (soft_dispatch, dispatch_only_core), :355-367 and
   ff_dpdk_if.c:420 (a port's nb_queues = its lcore_list length).
 * [kni] keys (ff_config.c:442-449) and ff_check_config's rules (:538-604).
 """
+import json
 from pathlib import Path
 
 import numpy as np
@@ -18,7 +21,8 @@ import pytest
 
 from yastack_amd import ffconfig as F
 
-REF_CFG = Path("/root/reference/fs/config")
+GOLDEN = Path(__file__).resolve().parent / "golden"
+REF_CFG = GOLDEN / "ff_config"
 
 # hand-derived: lcore_mask -> nb_procs; [port0] lcore_list -> nb_queues
 EXPECT = {
@@ -31,16 +35,21 @@ EXPECT = {
 }
 
 
-def _need(path: Path):
-    if not path.exists():
-        pytest.skip(f"{path} not present (reference not mounted)")
+def _recorded(rec):
+    """(events, error) as ref_ini_events gives them, from ref_ini_events.json."""
+    return [tuple(e) for e in rec["events"]], rec["error"]
+
+
+@pytest.fixture(scope="module")
+def ref_recorded():
+    return json.loads((GOLDEN / "ref_ini_events.json").read_text())
 
 
 @pytest.mark.parametrize("name", sorted(EXPECT))
-def test_reference_configs(name, oracle_mod):
+def test_reference_configs(name, oracle_mod, ref_recorded):
     path = REF_CFG / name
-    _need(path)
     ours = F.ini_events(path.read_bytes())
+    assert ours == _recorded(ref_recorded["configs"][name])
     ref = oracle_mod.ref_ini_events(path)
     if ref is not None:
         assert ours == ref
@@ -85,15 +94,23 @@ def _random_ini(rng) -> bytes:
     return head + text.encode("latin-1") + (eol.encode() if rng.random() < 0.7 else b"")
 
 
-def test_reader_vs_reference_generated(tmp_path, oracle_mod):
-    if oracle_mod.ref_ini_events(Path(__file__)) is None:
-        pytest.skip("oracle/_ref/libref_ini.so not built (reference not mounted)")
+def generated_inis():
+    """The files of test_reader_vs_reference_generated, in the order
+    golden/ref_ini_events.json holds the reference's answers (make_golden.py ref)."""
     rng = np.random.default_rng(642)
-    for i in range(400):
-        data = _random_ini(rng)
-        p = tmp_path / f"g{i}.ini"
-        p.write_bytes(data)
-        assert F.ini_events(data) == oracle_mod.ref_ini_events(p), data[:200]
+    return [_random_ini(rng) for _ in range(400)]
+
+
+def test_reader_vs_reference_generated(tmp_path, oracle_mod, ref_recorded):
+    live = oracle_mod.ref_ini_events(Path(__file__)) is not None
+    files, want = generated_inis(), ref_recorded["generated"]
+    assert len(files) == len(want) == 400
+    for i, (data, rec) in enumerate(zip(files, want)):
+        assert F.ini_events(data) == _recorded(rec), data[:200]
+        if live:
+            p = tmp_path / f"g{i}.ini"
+            p.write_bytes(data)
+            assert oracle_mod.ref_ini_events(p) == _recorded(rec), data[:200]
 
 
 def test_list_and_mask_rules():

@@ -106,14 +106,8 @@ def test_route_model_semantics(oracle_mod):
 
 
 # ---- pinned to the reference itself: oracle/_ref/libref_kni.so is
-# fs/lib/ff_dpdk_kni.c:51-123 compiled verbatim by oracle/build_ref.sh ----------
-
-def _ref_or_skip(oracle_mod):
-    import pytest
-
-    if oracle_mod.ref_kni() is None:
-        pytest.skip("oracle/_ref/libref_kni.so not built (reference not mounted)")
-
+# fs/lib/ff_dpdk_kni.c:51-123 compiled verbatim by oracle/build_ref.sh; what it
+# answers on these seeded inputs is recorded in golden/ref_kni.npz -------------
 
 def _random_port_list(rng):
     def num():
@@ -147,24 +141,32 @@ def _random_port_list(rng):
     return ",".join(pieces)
 
 
-def test_kni_set_bitmap_vs_reference(oracle_mod):
-    _ref_or_skip(oracle_mod)
+def bitmap_specs():
+    """Port lists of test_kni_set_bitmap_vs_reference, in the order
+    golden/ref_kni.npz holds the reference's bitmaps (make_golden.py ref)."""
     fixed = ["80", "80,443", "8000-8080", "80-", "-5", "90-80", "0-70000", "", ",", "80,,443",
              "65535", "65536", "65537", "-1", "1-", "a-b", "1,2-", "5-,7", "0", "10-20,15-25"]
-    for s in fixed + [None]:
-        assert np.array_equal(oracle_mod.kni_bitmap(s), oracle_mod.ref_kni_bitmap(s)), s
     rng = np.random.default_rng(20261016)
-    for _ in range(3000):
-        s = _random_port_list(rng)
-        assert np.array_equal(oracle_mod.kni_bitmap(s), oracle_mod.ref_kni_bitmap(s)), s
+    return fixed + [None] + [_random_port_list(rng) for _ in range(3000)]
 
 
-def test_port_lookup_vs_reference_get_bitmap(oracle_mod):
-    """protocol_filter's port test (ff_dpdk_kni.c:232-236, 244-248) against the
-    reference's get_bitmap on the dst_port as stored (network order read as a
-    little-endian uint16)."""
-    _ref_or_skip(oracle_mod)
-    R = oracle_mod.ref_kni()
+def test_kni_set_bitmap_vs_reference(oracle_mod, golden_dir):
+    """Against the reference's recorded bitmaps, and where oracle/_ref is built
+    against its compiled kni_set_bitmap as well."""
+    want = np.load(golden_dir / "ref_kni.npz")["bitmaps"]
+    specs = bitmap_specs()
+    assert want.shape == (len(specs), 8192) and len(specs) == 3021
+    live = oracle_mod.ref_kni() is not None
+    for s, bm in zip(specs, want):
+        assert np.array_equal(oracle_mod.kni_bitmap(s), bm), s
+        if live:
+            assert np.array_equal(oracle_mod.ref_kni_bitmap(s), bm), s
+
+
+def lookup_cases(oracle_mod):
+    """(raw dst_port, bitmap, spec, dport, proto, tcp, udp) per lookup of
+    test_port_lookup_vs_reference_get_bitmap, in the order golden/ref_kni.npz
+    holds the reference's get_bitmap(raw, bitmap) answers."""
     rng = np.random.default_rng(7)
     for trial in range(6):
         spec = _random_port_list(rng)
@@ -175,6 +177,22 @@ def test_port_lookup_vs_reference_get_bitmap(oracle_mod):
             dport = int(dport)
             raw = ((dport & 0xFF) << 8) | (dport >> 8)     # LE read of the network bytes
             for proto, bm in ((6, tcp), (17, udp)):
-                f = ipv4_frame("10.0.0.1", 1234, "10.0.0.2", dport, proto=proto)
-                want = 2 if R.ref_get_bitmap(raw, bm.ctypes.data) else -1
-                assert oracle_mod.protocol_filter(f, 64, True, tcp, udp) == want, (spec, dport)
+                yield raw, bm, spec, dport, proto, tcp, udp
+
+
+def test_port_lookup_vs_reference_get_bitmap(oracle_mod, golden_dir):
+    """protocol_filter's port test (ff_dpdk_kni.c:232-236, 244-248) against the
+    reference's get_bitmap on the dst_port as stored (network order read as a
+    little-endian uint16): its recorded answers, and where oracle/_ref is built
+    the compiled get_bitmap as well."""
+    hits = np.load(golden_dir / "ref_kni.npz")["hits"]
+    R = oracle_mod.ref_kni()
+    seen = 0
+    for (raw, bm, spec, dport, proto, tcp, udp), hit in zip(lookup_cases(oracle_mod), hits):
+        if R is not None:
+            assert bool(R.ref_get_bitmap(raw, bm.ctypes.data)) == bool(hit), (spec, dport)
+        f = ipv4_frame("10.0.0.1", 1234, "10.0.0.2", dport, proto=proto)
+        want = 2 if hit else -1
+        assert oracle_mod.protocol_filter(f, 64, True, tcp, udp) == want, (spec, dport)
+        seen += 1
+    assert seen == hits.size == 6 * 304 * 2

@@ -1,8 +1,9 @@
 """The oracle (CPU restatement) pinned against the reference's own vectors.
 
 Runs on CPU.  Pins, in order of strength:
-  * the reference's toeplitz_hash compiled from its source (oracle/_ref) on
-    random tuples — skipped where the reference is not mounted;
+  * the reference's toeplitz_hash on random tuples: its recorded answers
+    (golden/ref_thash.npz), and the engine compiled from its source
+    (oracle/_ref) where that is built;
   * the Intel 82599 verification suite held by dpdk/test/test/test_thash.c;
   * SURVEY.md §8(a)'s known answers from the reference toeplitz_dispatch;
   * the committed synth fixtures (hashes produced by the reference engine).
@@ -15,27 +16,39 @@ import pytest
 from frames import ipv4_frame
 
 
-def test_key_matches_reference(oracle_mod):
+def test_key_matches_reference(oracle_mod, golden_dir):
+    assert np.load(golden_dir / "ref_thash.npz")["key"].tobytes() == oracle_mod.MLX_KEY
     R = oracle_mod.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference not mounted)")
-    key = bytes(R.ref_default_rsskey()[i] for i in range(40))
-    assert key == oracle_mod.MLX_KEY
+    if R is not None:
+        key = bytes(R.ref_default_rsskey()[i] for i in range(40))
+        assert key == oracle_mod.MLX_KEY
 
 
-def test_engine_vs_reference_random(oracle_mod):
-    R = oracle_mod.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference not mounted)")
+def thash_cases():
+    """(keylen, key, data) of test_engine_vs_reference_random, in the order
+    golden/ref_thash.npz holds the reference's hashes (make_golden.py ref)."""
+    from oracle import oracle
+
     rng = np.random.default_rng(7)
-    keys = [oracle_mod.MLX_KEY, bytes(rng.integers(0, 256, 40, dtype=np.uint8))]
+    keys = [oracle.MLX_KEY, bytes(rng.integers(0, 256, 40, dtype=np.uint8))]
     for key in keys:
         for dl in (1, 4, 8, 12, 36):
             for kl in (4, 13, 40):
                 for _ in range(50):
-                    d = bytes(rng.integers(0, 256, dl, dtype=np.uint8))
-                    assert (oracle_mod.lib().oracle_toeplitz_hash(kl, key, dl, d)
-                            == R.ref_toeplitz_hash(kl, key, dl, d))
+                    yield kl, key, bytes(rng.integers(0, 256, dl, dtype=np.uint8))
+
+
+def test_engine_vs_reference_random(oracle_mod, golden_dir):
+    """Against the reference's recorded hashes, and where oracle/_ref is built
+    against its compiled toeplitz_hash as well."""
+    want = np.load(golden_dir / "ref_thash.npz")["hashes"]
+    R = oracle_mod.ref()
+    cases = list(thash_cases())
+    assert len(cases) == want.size == 1500
+    for (kl, key, d), h in zip(cases, want):
+        assert oracle_mod.lib().oracle_toeplitz_hash(kl, key, len(d), d) == int(h)
+        if R is not None:
+            assert R.ref_toeplitz_hash(kl, key, len(d), d) == int(h)
 
 
 def test_82599_vectors(oracle_mod, golden_dir):

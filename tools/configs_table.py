@@ -46,7 +46,7 @@ def main():
     args = ap.parse_args()
     rows = []
     for cid, prof, desc, extra in CONFIGS + (QUEUES if args.queues else []):
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--profile", prof, "--steps",
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--profile", prof, "--steps",
                str(args.steps), "--cpu-seconds", str(args.cpu_seconds if not extra else 0),
                "--pcie", "0", "--extra-configs=", *extra]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

@@ -16,7 +16,7 @@ out=gpurun_out/abl_$tag.log
 for round in 1 2; do
     for np in $qs; do
         for lib in $libs; do
-            B="--profile tcp4 --nb-procs $np --steps 30 --warmup 10 --cpu-seconds 0 --pcie 0 --check 0 $extra"
+            B="--full --profile tcp4 --nb-procs $np --steps 30 --warmup 10 --cpu-seconds 0 --pcie 0 --check 0 $extra"
             echo "== r$round q$np $(basename $lib)" >> "$out"
             if [ "$lib" = cur ]; then
                 timeout -k 10 240 python bench.py $B >> "$out" 2>&1 || { echo "$lib q$np rc=$?"; exit 1; }

@@ -15,7 +15,7 @@ export TMPDIR=/tmp PYTHONUNBUFFERED=1
 log=gpurun_out/bench_n${n}_$prof.log
 YRSS_BENCH_ONE_DEVICE=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$n" \
-    --profile "$prof" --steps 20 --warmup 5 --pcie 0 "$@" > "$log" 2>&1 \
+    --profile "$prof" --steps 20 --warmup 5 --full --pcie 0 "$@" > "$log" 2>&1 \
     || { tail -20 "$log"; exit 1; }
 grep '^{"metric"' "$log" | python -c '
 import json, sys

@@ -196,6 +196,63 @@ struct yrss_dev_batch {
 };
 int yrss_dispatch_dev_ex(yrss_ctx *ctx, const struct yrss_dev_batch *b, void *stream);
 
+/* ---- segmented per-queue lists (the parse kernel's own output) ---------------- */
+
+/* The reference never builds a batch-wide list: process_packets enqueues
+ * burst by burst, in order, into dispatch_ring[port][q] (ff_dpdk_if.c:1087-1093
+ * inside the :1674-1683 loop).  This form is that contract: the batch is cut
+ * into segments of YRSS_SEG_PKTS consecutive packets (segment s = packets
+ * [256 s, min(256 s + 256, n)), nseg = ceil(n / 256)), each with its own
+ * finished lists over nbk = nb_queues + 1 buckets (the last one holds the
+ * packets process_packets frees, :1080-1083, as in yrss_dispatch_dev):
+ *   seg_idx   n x uint8.  Bytes [256 s, 256 s + len_s) are the segment-local
+ *             indices (0..255) of segment s's packets, grouped by bucket in
+ *             bucket order, FIFO inside each bucket.  Packet = 256 s + byte.
+ *   seg_off   nseg x (nbk + 1) x uint16, segment-major.  Bucket b of segment
+ *             s = seg_idx[256 s + seg_off[s][b] .. 256 s + seg_off[s][b+1]);
+ *             seg_off[s][0] == 0, seg_off[s][nbk] == len_s.
+ * Walking the segments in order and appending each segment's bucket b to ring
+ * b gives bucket b's list of yrss_dispatch_dev, so every queue stays FIFO
+ * exactly as with the reference's per-burst rte_ring_enqueue_burst.
+ * The parse kernel writes the lists itself, with each segment's q and hash:
+ * one launch, no scan or scatter kernel, 1 byte per packet. */
+#define YRSS_SEG_PKTS 256
+#define YRSS_SEG_MAX_BUCKETS 16
+#define YRSS_SEG_MAX_BATCH (1u << 24)
+
+struct yrss_dev_seg_batch {
+    const uint8_t *win;       /* as d_win of yrss_dispatch_dev          */
+    uint32_t win_stride;
+    uint32_t n;
+    const uint16_t *len;
+    int16_t *q;
+    uint32_t *hash;           /* may be NULL                            */
+    int8_t *filter;           /* YRSS_FILTER_* per packet, or NULL      */
+    uint8_t *seg_idx;         /* n bytes, 16-byte aligned               */
+    uint16_t *seg_off;        /* ceil(n / 256) x (nb_queues + 2)        */
+};
+/* Asynchronous, with the stream and workspace rules of yrss_dispatch_dev (the
+ * stream switch waits on the device, -EBUSY while a YRSS_F_ASYNC burst is
+ * pending, a resident worker is retired first).  Checked before anything is
+ * launched: nb_queues + 1 <= YRSS_SEG_MAX_BUCKETS, else -ENOTSUP;
+ * n <= YRSS_SEG_MAX_BATCH and the alignments of yrss_dispatch_dev plus
+ * seg_idx (16 bytes) and seg_off (2), else -EINVAL.  Segments are
+ * independent, so a larger batch is split at any multiple of 256.  n == 0
+ * launches nothing; every n >= 1 runs the parse kernel (no one-launch
+ * shortcut).  It leaves the list workspace of yrss_dispatch_dev untouched, so
+ * both forms may alternate on one context.  A list slot outside its segment
+ * is not stored and sets the fault record (YRSS_FAULT_LIST_RANGE, kernel
+ * YRSS_K_PARSE_HASH; yrss_status). */
+int yrss_dispatch_dev_seg(yrss_ctx *ctx, const struct yrss_dev_seg_batch *b, void *stream);
+
+/* Host-only: the segmented form as the qidx (n x uint32) / qstart (nbk + 1
+ * offsets) of yrss_dispatch_dev.  The arrays are not trusted: every offset
+ * row must be monotone from 0 to len_s and every index < len_s, else -EINVAL
+ * (nothing outside the arrays' stated sizes is read or written).
+ * yastack_amd/segments.py is the Python twin. */
+int yrss_seg_to_lists(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
+                      uint32_t nbk, uint32_t *out_qidx, uint32_t *out_qstart);
+
 
 /* ---- host-resident dispatch (the drop-in burst hook) ------------------------ */
 

@@ -29,6 +29,10 @@ WIN_MIN = 64
 WIN_FULL = 80
 MAX_QUEUES = 256
 MAX_PROCS = 4096
+# segmented per-queue lists (yrss_dispatch_dev_seg)
+SEG_PKTS = 256
+SEG_MAX_BUCKETS = 16
+SEG_MAX_BATCH = 1 << 24
 F_WRITE_RSS = 0x1
 F_ASYNC = 0x2
 
@@ -105,6 +109,20 @@ class DevBatch(ctypes.Structure):
         ("qidx", ctypes.c_void_p),
         ("qstart", ctypes.c_void_p),
         ("filter", ctypes.c_void_p),
+    ]
+
+
+class DevSegBatch(ctypes.Structure):
+    _fields_ = [
+        ("win", ctypes.c_void_p),
+        ("win_stride", ctypes.c_uint32),
+        ("n", ctypes.c_uint32),
+        ("len", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("hash", ctypes.c_void_p),
+        ("filter", ctypes.c_void_p),
+        ("seg_idx", ctypes.c_void_p),
+        ("seg_off", ctypes.c_void_p),
     ]
 
 
@@ -221,6 +239,8 @@ _PROTOS = {
     "yrss_set_kni": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.c_char_p]),
     "yrss_dispatch_dev_ex": (ctypes.c_int, [_vp, ctypes.POINTER(DevBatch), _vp]),
+    "yrss_dispatch_dev_seg": (ctypes.c_int, [_vp, ctypes.POINTER(DevSegBatch), _vp]),
+    "yrss_seg_to_lists": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "yrss_dispatch_burst_zc": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32]),
     "yrss_dispatch_frames_zc": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "yrss_register_host_memory": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
@@ -236,6 +256,9 @@ _PROTOS = {
                                         ctypes.POINTER(RouteOps), _vp, _vp,
                                         ctypes.POINTER(RouteResult)]),
 }
+
+# entry points of the segmented list form (absent from older builds, see load())
+_SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists")
 
 # include/yrss_test_hooks.h (libyrss_test.so)
 _TEST_PROTOS = {
@@ -278,6 +301,10 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover - environment specific
         raise YrssLibraryError(f"cannot load {p}: {e}") from e
     for name, (res, args) in _PROTOS.items():
+        # a build of an older commit, loaded by path for an A/B, may predate
+        # the newest entry points; the in-tree library must have every one
+        if path is not None and name in _SINCE_SEG and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -109,6 +109,9 @@ struct ParseParams {
     uint32_t *rbin;       // with tot_acc: [nb][kLbMaxWgs] counts per line-scatter range
     uint32_t rbin_chunks; // chunks a range (a multiple of 8)
     uint32_t kwin[96];    // key window at every tuple bit position
+    uint8_t *seg_idx;     // kCount == 3: per 256-packet segment, its packets' segment-local
+                          // indices grouped by bucket (yrss_dispatch_dev_seg)
+    uint16_t *seg_off;    // kCount == 3: [segments][nb + 1] bucket offsets inside a segment
 };
 
 struct ScatterParams {
@@ -398,6 +401,64 @@ __device__ __forceinline__ void flush_out(const ParseParams &P, const uint16_t *
     }
 }
 
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane);
+
+// kCount == 3 (yrss_dispatch_dev_seg): the finished per-queue lists of one
+// 256-packet segment, written at the chunk's flush from what the wave already
+// holds in LDS: the chunk's q and in-bucket ranks (process_tile) and its
+// per-bucket counts (cnt, the wave's count slot, zeroed again here for the
+// wave's next chunk).  Lane b's exclusive prefix of the counts is bucket b's
+// offset inside the segment (lane nb: the segment's length); packet e's byte
+// goes to list[offset[bucket] + rank] (the list: 256 B of the wave's idle
+// count slots), guarded like every list slot here.  A whole number of tiles
+// goes out as 16-byte write-through stores, the batch-end remainder
+// lane-granular; resources sized to the valid bytes drop the lanes past the
+// end, as in flush_out.  One byte a packet and nb + 1 offsets a segment:
+// the stand-in for the reference's per-burst enqueue into
+// dispatch_ring[port][q] (ff_dpdk_if.c:1087-1093 inside the :1674-1683 loop).
+__device__ __forceinline__ void flush_seg(const ParseParams &P, const uint16_t *oq,
+                                          const uint16_t *orank, uint32_t *cnt, uint8_t *list,
+                                          uint32_t t_first, uint32_t ntiles, uint32_t lane)
+{
+    const uint32_t nv = min(ntiles * (uint32_t)kTile, P.n - t_first);
+    wave_lds_sync();
+    const uint32_t c = lane < P.nb ? cnt[lane] : 0u;
+    if (lane < P.nb)
+        cnt[lane] = 0u;
+    const uint32_t excl = wave_incl_scan(c, lane) - c;
+    for (uint32_t j = 0; j < ntiles; ++j) {
+        const uint32_t e = j * kTile + lane;
+        // (lanes past the end read stale q: the bucket stays a valid lane)
+        const uint32_t bkt = bucket_of((int)(int16_t)oq[e], P.nq);
+        const uint32_t pos = (uint32_t)__shfl((int)excl, (int)bkt, kWave) + orank[e];
+        if (e < nv) {
+            if (pos < nv)
+                list[pos] = (uint8_t)e;
+            else
+                report_fault(P.fault, YRSS_FAULT_LIST_RANGE, YRSS_K_PARSE_HASH, t_first + e, pos);
+        }
+    }
+    wave_lds_sync();
+    const __amdgpu_buffer_rsrc_t rl =
+        __builtin_amdgcn_make_buffer_rsrc(P.seg_idx + t_first, 0, (int)nv, kRsrcWord3);
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
+        P.seg_off + (size_t)(t_first / (kOutTiles * kTile)) * (P.nb + 1u), 0,
+        (int)((P.nb + 1u) * 2u), kRsrcWord3);
+    if (P.out16 && nv == ntiles * (uint32_t)kTile) {
+        const uint32_t nl = nv >> 4;
+        const u32x4 vl = *reinterpret_cast<const u32x4 *>(list + 16u * min(lane, nl - 1u));
+        if (lane < nl)
+            __builtin_amdgcn_raw_buffer_store_b128(vl, rl, (int)(lane * 16u), 0, 16);
+    } else {
+        for (uint32_t j = 0; j < ntiles; ++j) {
+            const uint32_t e = j * kTile + lane;
+            __builtin_amdgcn_raw_buffer_store_b8(list[e], rl, (int)e, 0, 0);
+        }
+    }
+    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)excl, ro, (int)(lane * 2u), 0, 0);
+    wave_lds_sync();
+}
+
 template <int kCount, bool kFilter>
 __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_t *tbl,
                                              const uint32_t *kni, u32x4 *stage, uint32_t *cnt,
@@ -538,12 +599,13 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
         const uint64_t peers = peer_mask(bkt, valid, P.nb);
         const uint64_t lt = lane_lt_mask(lane);
         const bool leader = valid && (peers & lt) == 0;
-        if (kCount == 2) {
+        if (kCount >= 2) {
             uint32_t before = 0;
             if (leader)
                 before = atomicAdd(&cnt[bkt], (uint32_t)__popcll(peers));
             const int ll = peers ? __builtin_ctzll(peers) : (int)lane;
-            const uint32_t tag = P.rank_pack ? bkt << (P.ct_shift + 6u) : 0u;
+            // (kCount == 3, the segmented lists: the plain rank, no bucket tag)
+            const uint32_t tag = kCount == 2 && P.rank_pack ? bkt << (P.ct_shift + 6u) : 0u;
             ob.r[lane] = (uint16_t)(tag | (__shfl(before, ll, kWave) + (uint32_t)__popcll(peers & lt)));
         } else if (leader) {
             atomicAdd(&cnt[bkt], (uint32_t)__popcll(peers));
@@ -556,6 +618,10 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
 //   kCount   1: also count packets per bucket per chunk (per-queue lists on);
 //            2: and write each packet's rank among its chunk's packets of its
 //            bucket (the ranked scatter places packets by it)
+//            3: segmented per-queue lists (yrss_dispatch_dev_seg): the ranks
+//            and counts stay in LDS and each 4-tile chunk's finished lists
+//            leave with its q and hash (flush_seg); no rank stream, no
+//            per-chunk counts, no totals: nothing for a second kernel
 //   kFilter  also classify protocol_filter / KNI (one byte per packet)
 //   kBlock   workgroup size (256/512): waves per CU, one key table per group
 // Window loads are non-temporal (streaming): ~25 % faster than default-policy
@@ -614,7 +680,8 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
     // check sits outside the loop: a fault-report branch inside it cost the
     // loop's load scheduling)
     bool slots_ok = true;   // (the wave still takes part in the workgroup's barriers)
-    if (kCount) {
+    constexpr bool kSeg = kCount == 3;   // one count slot, reused chunk after chunk
+    if (kCount && !kSeg) {
         const uint32_t own = P.nchunk > gw ? (P.nchunk - gw + W - 1u) / W : 0u;
         if (own * P.nb > kCntWords) {
             slots_ok = false;
@@ -629,7 +696,7 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
         if (c >= P.nchunk || t >= P.n)
             return false;
         t0 = (uint32_t)t;
-        slot = kk;
+        slot = kSeg ? 0u : kk;
         return true;
     };
     // outputs are buffered per batch of up to kOutTiles consecutive tiles of a
@@ -640,9 +707,13 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
         return OutSlot{oq + j, oh + j, of + j, orank + j};
     };
     auto after = [&](uint32_t i, uint32_t t0, bool last) {
-        if (((i + 1u) & fb_mask) == 0u || last)
+        if (((i + 1u) & fb_mask) == 0u || last) {
             flush_out<kFilter, kCount == 2>(P, oq, oh, of, orank, t0 - (i & fb_mask) * kTile,
                                             (i & fb_mask) + 1u, lane);
+            if (kSeg)   // (the list: words 64..127 of the wave's count slots)
+                flush_seg(P, oq, orank, cnt_w, reinterpret_cast<uint8_t *>(cnt_w + 64),
+                          t0 - (i & fb_mask) * kTile, (i & fb_mask) + 1u, lane);
+        }
     };
     constexpr int kC = kCount;
     uint32_t tA = 0, sA = 0, tB = 0, sB = 0;
@@ -667,7 +738,7 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
                 break;
         }
     }
-    if (kCount) {
+    if (kCount && !kSeg) {
         // Workgroup flush: for its j-th chunk each of the 8 waves owns column
         // blockIdx.x * 8 + w + j * W, so the workgroup's columns of round j
         // are 8 consecutive words of every bucket row.  Thread e takes wave
@@ -3287,9 +3358,13 @@ uint32_t resident_blocks(yrss_ctx *c, const void *fn, uint32_t block, uint32_t l
 
 typedef void (*ParseKernel)(ParseParams);
 
-// count: 0 none, 1 per-chunk counts, 2 counts + per-packet chunk ranks
+// count: 0 none, 1 per-chunk counts, 2 counts + per-packet chunk ranks,
+// 3 segmented lists (yrss_dispatch_dev_seg only)
 ParseKernel pick_parse(int count, bool filter)
 {
+    if (count == 3)
+        return filter ? yrss_parse_hash<3, true, kParseBlock>
+                      : yrss_parse_hash<3, false, kParseBlock>;
     if (filter)
         return count == 2 ? yrss_parse_hash<2, true, kParseBlock>
                : count    ? yrss_parse_hash<1, true, kParseBlock>
@@ -4292,6 +4367,81 @@ int yrss_dispatch_dev(yrss_ctx *c, const uint8_t *d_win, uint32_t win_stride,
     b.qstart = d_qstart;
     b.filter = nullptr;
     return yrss_dispatch_dev_ex(c, &b, stream);
+}
+
+// The segmented list form: one launch of the parse kernel's kCount == 3
+// variant, whatever n (no one-launch shortcut, no scan, no scatter).  It
+// touches none of the compaction workspace (no ranks, counts or totals), so
+// it may sit between two yrss_dispatch_dev batches; it keeps their stream
+// rules because it shares the context's fault record and timing events.
+int yrss_dispatch_dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, void *stream)
+{
+    if (!c || !b)
+        return -EINVAL;
+    if (c->pend.active)      // the host burst in flight owns the context
+        return -EBUSY;
+    const uint32_t n = b->n;
+    if (c->nb > YRSS_SEG_MAX_BUCKETS)
+        return -ENOTSUP;
+    if (b->win_stride < YRSS_WIN_MIN || (b->win_stride & 15u) || n > YRSS_SEG_MAX_BATCH)
+        return -EINVAL;
+    if (n && (!b->win || !b->len || !b->q || !b->seg_idx || !b->seg_off))
+        return -EINVAL;
+    if (((uintptr_t)b->win & 15u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->q & 1u) ||
+        ((uintptr_t)b->hash & 3u) || ((uintptr_t)b->seg_idx & 15u) ||
+        ((uintptr_t)b->seg_off & 1u))
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->w.running) {      // the resident worker holds CUs the grid needs
+        const int rc = worker_halt(c);
+        if (rc)
+            return rc;
+    }
+    if (c->last_stream_valid && c->last_stream != s) {
+        YRSS_HIP(hipEventRecord(c->switch_ev, c->last_stream));
+        YRSS_HIP(hipStreamWaitEvent(s, c->switch_ev, 0));
+    }
+    c->last_stream = s;
+    c->last_stream_valid = true;
+    const bool filter = b->filter != nullptr;
+    ParseParams P = c->proto;
+    P.win = b->win;
+    P.len = b->len;
+    P.q = b->q;
+    P.hash = b->hash;
+    P.seg_cnt = nullptr;
+    P.rank = nullptr;
+    P.fault = c->d_fault_rec;
+    P.n = n;
+    P.stride = b->win_stride;
+    // a chunk is a segment: 4 tiles, the parse kernel's output burst
+    // (yrss_tuning.chunk_tiles does not apply)
+    static_assert(YRSS_SEG_PKTS == kOutTiles * kTile, "a segment is one output burst");
+    static_assert(YRSS_SEG_MAX_BATCH / YRSS_SEG_PKTS <= kMaxChunks, "chunks of one launch");
+    static_assert(64u + YRSS_SEG_PKTS / 4u <= kCntWords && YRSS_SEG_MAX_BUCKETS <= 64u,
+                  "the list sits in the count slots, behind the one slot in use");
+    P.chunk = YRSS_SEG_PKTS;
+    P.ct_shift = 2;
+    P.nchunk = (n + YRSS_SEG_PKTS - 1u) / YRSS_SEG_PKTS;
+    P.ncol = 0;
+    P.filter = b->filter;
+    P.kni_bm = c->d_kni;
+    P.kni_enable = c->kni_enable ? 1u : 0u;
+    P.rank_pack = 0;
+    P.tot_acc = nullptr;
+    P.rbin = nullptr;
+    P.rbin_chunks = 0;
+    P.seg_idx = b->seg_idx;
+    P.seg_off = b->seg_off;
+    {
+        Timed t(c, YRSS_K_PARSE_HASH);
+        hipExtLaunchKernelGGL(pick_parse(3, filter), dim3(grid_for(c, n)), dim3(kParseBlock),
+                              (uint32_t)parse_lds(filter), s, t.a, t.b, 0, P);
+    }
+    YRSS_HIP(hipGetLastError());
+    return 0;
 }
 
 int yrss_dispatch_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len,

@@ -49,6 +49,32 @@ class DispatchResult:
         return self.qidx[int(s[b]):int(s[b + 1])]
 
 
+@dataclass
+class SegResult:
+    """Per-packet queue/hash plus the segmented per-queue lists
+    (``yrss_dispatch_dev_seg``): the batch in segments of ``abi.SEG_PKTS``
+    consecutive packets, each with its own finished lists.
+
+    ``seg_idx``   n x uint8: bytes [256 s, 256 s + len_s) are segment s's
+                  segment-local packet indices, grouped by bucket, FIFO inside
+    ``seg_off``   nseg x (nb_queues + 2) uint16 offsets into those bytes
+    """
+
+    q: object
+    hash: object
+    filter: object
+    seg_idx: object
+    seg_off: object
+    n: int = 0
+
+    def segment(self, s: int, b: int):
+        """Segment-local indices of segment s dispatched to queue b (b ==
+        nb_queues: dropped); packet number = 256 * s + index."""
+        o = self.seg_off[s]
+        base = s * abi.SEG_PKTS
+        return self.seg_idx[base + int(o[b]):base + int(o[b + 1])]
+
+
 def _check_dev_sizes(n, stride, win, lens, out, nb_queues):
     """The C ABI takes raw device pointers and cannot see the buffers' sizes: a
     batch larger than its buffers would fault the GPU.  Refuse it here."""
@@ -67,6 +93,26 @@ def _check_dev_sizes(n, stride, win, lens, out, nb_queues):
         need.append(("qidx", out.qidx, 4 * n))
     if out.qstart is not None:
         need.append(("qstart", out.qstart, 4 * (nb_queues + 2)))
+    if out.filter is not None:
+        need.append(("filter", out.filter, n))
+    for name, t, b in need:
+        if nbytes(t) < b:
+            raise ValueError(f"{name} holds {nbytes(t)} bytes, the batch of {n} needs {b}")
+
+
+def _check_seg_sizes(n, stride, win, lens, out, nb_queues):
+    """As _check_dev_sizes, for the segmented form's buffers."""
+    def nbytes(t):
+        return 0 if t is None else int(t.numel()) * int(t.element_size())
+    if n < 0:
+        raise ValueError("negative batch size")
+    if n == 0:
+        return
+    nseg = -(-n // abi.SEG_PKTS)
+    need = [("win", win, n * stride), ("lens", lens, 2 * n), ("q", out.q, 2 * n),
+            ("seg_idx", out.seg_idx, n), ("seg_off", out.seg_off, 2 * nseg * (nb_queues + 2))]
+    if out.hash is not None:
+        need.append(("hash", out.hash, 4 * n))
     if out.filter is not None:
         need.append(("filter", out.filter, n))
     for name, t, b in need:
@@ -189,6 +235,33 @@ class SoftRss:
         rc = self._lib.yrss_dispatch_dev_ex(self._ctx, ctypes.byref(b), self._stream(stream))
         abi.check(rc, "yrss_dispatch_dev_ex")
         return out
+
+    def dispatch_dev_seg(self, win, lens, stride: int, n: int | None = None, *, out=None,
+                         want_hash: bool = True, want_filter: bool = False,
+                         stream=None) -> SegResult:
+        """Classify n packets resident in HBM and return the per-queue lists in
+        segments of 256 packets, written by the parse kernel itself
+        (``yrss_dispatch_dev_seg``: one launch; nb_queues + 1 <= 16, n <= 2^24)."""
+        n = int(lens.numel()) if n is None else n
+        if out is None:
+            out = self.alloc_seg_out(n, lens.device, want_hash, want_filter)
+        _check_seg_sizes(n, stride, win, lens, out, self.nb_queues)
+        b = abi.DevSegBatch(_ptr(win), stride, n, _ptr(lens), _ptr(out.q), _ptr(out.hash),
+                            _ptr(out.filter), _ptr(out.seg_idx), _ptr(out.seg_off))
+        rc = self._lib.yrss_dispatch_dev_seg(self._ctx, ctypes.byref(b), self._stream(stream))
+        abi.check(rc, "yrss_dispatch_dev_seg")
+        out.n = n
+        return out
+
+    def alloc_seg_out(self, n: int, dev, want_hash=True, want_filter=False) -> SegResult:
+        torch = self._torch()
+        nseg = max(-(-n // abi.SEG_PKTS), 1)
+        q = torch.empty(max(n, 1), dtype=torch.int16, device=dev)
+        h = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if want_hash else None
+        f = torch.empty(max(n, 1), dtype=torch.int8, device=dev) if want_filter else None
+        si = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        so = torch.empty((nseg, self.nb_queues + 2), dtype=torch.int16, device=dev)
+        return SegResult(q, h, f, si, so, n)
 
     def alloc_out(self, n: int, dev, want_hash=True, compact=True,
                   want_filter=False) -> DispatchResult:

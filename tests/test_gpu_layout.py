@@ -40,14 +40,26 @@ def to_np(t, dtype):
 KNI = ("accept", "0-32767", "1000-40000,53,123")
 
 
-def check(eng, oracle_mod, cfg_tuple, profile, n, stride=64, first=0, want_filter=False):
+def upload(traffic, dev):
+    """Host-built (win uint8, lens uint16) arrays as device tensors."""
+    win, lens = traffic
+    return (torch.from_numpy(np.ascontiguousarray(win)).to(dev),
+            torch.from_numpy(np.ascontiguousarray(lens).view(np.int16)).to(dev))
+
+
+def check(eng, oracle_mod, cfg_tuple, profile, n, stride=64, first=0, want_filter=False,
+          traffic=None, out=None):
     """One device batch against the oracle: q, hash, qstart, qidx (and the
-    filter class when asked), plus an empty fault record."""
+    filter class when asked), plus an empty fault record.  traffic: host-built
+    (win, lens) instead of a synthetic profile; out: the caller's buffers."""
     npr, nq, soft, only = cfg_tuple
     if want_filter:
         eng.set_kni(True, *KNI)
-    win, lens = eng.synth(profile, n, first, stride=stride)
-    res = eng.dispatch_dev(win, lens, stride, n, want_filter=want_filter)
+    if traffic is None:
+        win, lens = eng.synth(profile, n, first, stride=stride)
+    else:
+        win, lens = upload(traffic, torch.device("cuda", 0))
+    res = eng.dispatch_dev(win, lens, stride, n, want_filter=want_filter, out=out)
     torch.cuda.synchronize()
     fault = eng.fault_info()
     assert fault[0] == abi.FAULT_NONE, f"device guard fired: {fault}"

@@ -39,11 +39,17 @@ def padded_out(eng, n, dev, want_filter=False):
         seg_off=torch.full((nseg + 1, eng.nb_queues + 2), 0x7777, dtype=torch.int16, device=dev))
 
 
-def check_seg(eng, oracle_mod, cfg, profile, n, stride=64, first=0, want_filter=False):
-    """One segmented batch against the oracle; returns (result, q_ref)."""
+def check_seg(eng, oracle_mod, cfg, profile, n, stride=64, first=0, want_filter=False,
+              traffic=None):
+    """One segmented batch against the oracle; returns (result, q_ref).
+    traffic: host-built (win uint8, lens uint16) instead of a synthetic profile."""
     npr, nq, soft, only = cfg
     dev = torch.device("cuda", 0)
-    win, lens = eng.synth(profile, n, first, stride=stride)
+    if traffic is None:
+        win, lens = eng.synth(profile, n, first, stride=stride)
+    else:
+        win = torch.from_numpy(np.ascontiguousarray(traffic[0])).to(dev)
+        lens = torch.from_numpy(np.ascontiguousarray(traffic[1]).view(np.int16)).to(dev)
     out = padded_out(eng, n, dev, want_filter)
     res = eng.dispatch_dev_seg(win, lens, stride, n, out=out)
     torch.cuda.synchronize()

@@ -253,6 +253,88 @@ int yrss_dispatch_dev_seg(yrss_ctx *ctx, const struct yrss_dev_seg_batch *b, voi
 int yrss_seg_to_lists(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
                       uint32_t nbk, uint32_t *out_qidx, uint32_t *out_qstart);
 
+/* ---- routed segmented lists: process_packets' hand-off classes ---------------- */
+
+/* yrss_dispatch_dev_seg's lists answer "which queue".  process_packets does
+ * more with a packet whose queue is the dispatcher lcore's own (queue_id):
+ * ARP is cloned to every other ring (ff_dpdk_if.c:1097-1129), the KNI rule
+ * hands packets to KNI (:1132-1135), the rest is delivered locally (:1137).
+ * This form is the same segmented layout over nrb = nb_queues + 3 route
+ * buckets, decided by the parse kernel from the queue and the protocol_filter
+ * class it already holds, so the host performs the whole hand-off with list
+ * walks (yrss_route_seg) and reads neither q nor filter.  With nq = nb_queues,
+ * f the YRSS_FILTER_* class and the context's KNI state (yrss_set_kni):
+ *   b < nq, b != queue_id   q == b: for dispatch_ring[port][b] (:1087-1093)
+ *   queue_id (if < nq)      local delivery (ff_veth_input): q == queue_id,
+ *                           neither ARP nor sent to KNI; YRSS_FILTER_TRUNC /
+ *                           YRSS_FILTER_LOOP packets stay here, as in
+ *                           yrss_route_burst
+ *   nq                      freed: q < 0 || q >= nq (:1080-1083)
+ *   nq + 1                  KNI: q == queue_id, KNI on and (f == YRSS_FILTER_KNI
+ *                           under "accept" or f == YRSS_FILTER_UNKNOWN under
+ *                           "reject")
+ *   nq + 2                  ARP on the local queue: q == queue_id,
+ *                           f == YRSS_FILTER_ARP, KNI on or off
+ * queue_id >= nq is legal: no packet is local, buckets nq + 1 and nq + 2 stay
+ * empty.  seg_idx is n x uint8 and seg_off ceil(n / 256) x (nrb + 1) uint16,
+ * exactly as in yrss_dispatch_dev_seg with nrb in place of nbk: every bucket
+ * FIFO, seg_off[s][0] == 0, seg_off[s][nrb] == len_s. */
+#define YRSS_ROUTE_SEG_MAX_QUEUES 13   /* nb_queues + 3 <= YRSS_SEG_MAX_BUCKETS */
+
+struct yrss_dev_route_batch {   /* yrss_dev_seg_batch + queue_id */
+    const uint8_t *win;       /* as d_win of yrss_dispatch_dev          */
+    uint32_t win_stride;
+    uint32_t n;
+    const uint16_t *len;
+    int16_t *q;
+    uint32_t *hash;           /* may be NULL                            */
+    int8_t *filter;           /* YRSS_FILTER_* per packet, or NULL      */
+    uint8_t *seg_idx;         /* n bytes, 16-byte aligned               */
+    uint16_t *seg_off;        /* ceil(n / 256) x (nb_queues + 4)        */
+    uint16_t queue_id;        /* the dispatcher lcore's own queue       */
+};
+/* One launch of the parse kernel, asynchronous, with every rule of
+ * yrss_dispatch_dev_seg: stream switch, -EBUSY while a YRSS_F_ASYNC burst is
+ * pending, a resident worker retired first, the alignments, n <=
+ * YRSS_SEG_MAX_BATCH (else -EINVAL), n == 0 launches nothing, the list
+ * workspace of yrss_dispatch_dev untouched, the same guard and fault record,
+ * the same timing slot (YRSS_K_PARSE_HASH).  nb_queues >
+ * YRSS_ROUTE_SEG_MAX_QUEUES is refused with -ENOTSUP before anything is
+ * launched.  The KNI state is the one yrss_set_kni last set, read at the call.
+ * q, hash and (when filter is not NULL) filter are written as by
+ * yrss_dispatch_dev_seg; the classes are computed whether or not filter is
+ * stored. */
+int yrss_route_dev_seg(yrss_ctx *ctx, const struct yrss_dev_route_batch *b, void *stream);
+
+struct yrss_route_ops;
+struct yrss_route_result;
+/* Host-only: process_packets' hand-off from routed segments, segment by
+ * segment in order; per segment what yrss_route_burst does for a burst of 256.
+ * objs[i] is packet i's mbuf; ops, out_local, out_kni and res are those of
+ * yrss_route_burst (below); kni_clone is its "KNI on && kni_primary".
+ *   - every ARP-bucket packet, in packet order: ops->clone for each queue
+ *     j != queue_id in queue order, then the KNI clone (queue 0xFFFF) when
+ *     kni_clone is set
+ *   - one ops->enqueue per ring with anything to take: bucket j merged by
+ *     packet index with the successful ARP clones for j; the tail the ring
+ *     refuses is released (n_freed); n_ring[j] accumulates over the segments
+ *   - bucket nq is released (n_freed)
+ *   - out_local: the local bucket merged by index with the ARP bucket (n_arp)
+ *   - out_kni: the KNI bucket merged by index with the KNI clones
+ * n_unresolved counts the local bucket's YRSS_FILTER_TRUNC / YRSS_FILTER_LOOP
+ * packets when filter (n x int8, as the kernel wrote it) is given; with
+ * filter == NULL it is 0 and those packets are simply part of out_local.
+ * The arrays are not trusted: all of them are validated first, by the rules of
+ * yrss_seg_to_lists (rows monotone from 0 to len_s, every index < len_s,
+ * nb_queues + 3 <= YRSS_SEG_MAX_BUCKETS), and a failure returns -EINVAL before
+ * any callback is invoked.  out_local and out_kni need room for n each (a packet
+ * adds itself or its one KNI clone to out_kni, never both). */
+int yrss_route_seg(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
+                   uint16_t nb_queues, uint16_t queue_id, int kni_clone,
+                   const int8_t *filter, void *const *objs,
+                   const struct yrss_route_ops *ops, void **out_local, void **out_kni,
+                   struct yrss_route_result *res);
+
 
 /* ---- host-resident dispatch (the drop-in burst hook) ------------------------ */
 

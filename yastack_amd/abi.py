@@ -33,6 +33,8 @@ MAX_PROCS = 4096
 SEG_PKTS = 256
 SEG_MAX_BUCKETS = 16
 SEG_MAX_BATCH = 1 << 24
+# routed segmented lists (yrss_route_dev_seg): nb_queues + 3 route buckets
+ROUTE_SEG_MAX_QUEUES = 13
 F_WRITE_RSS = 0x1
 F_ASYNC = 0x2
 
@@ -124,6 +126,10 @@ class DevSegBatch(ctypes.Structure):
         ("seg_idx", ctypes.c_void_p),
         ("seg_off", ctypes.c_void_p),
     ]
+
+
+class DevRouteBatch(ctypes.Structure):
+    _fields_ = DevSegBatch._fields_ + [("queue_id", ctypes.c_uint16)]
 
 
 ENQUEUE_FN = ctypes.CFUNCTYPE(ctypes.c_uint, ctypes.c_void_p, ctypes.c_uint16,
@@ -241,6 +247,10 @@ _PROTOS = {
     "yrss_dispatch_dev_ex": (ctypes.c_int, [_vp, ctypes.POINTER(DevBatch), _vp]),
     "yrss_dispatch_dev_seg": (ctypes.c_int, [_vp, ctypes.POINTER(DevSegBatch), _vp]),
     "yrss_seg_to_lists": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "yrss_route_dev_seg": (ctypes.c_int, [_vp, ctypes.POINTER(DevRouteBatch), _vp]),
+    "yrss_route_seg": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_uint16, ctypes.c_uint16,
+                                      ctypes.c_int, _vp, _vp, ctypes.POINTER(RouteOps), _vp, _vp,
+                                      ctypes.POINTER(RouteResult)]),
     "yrss_dispatch_burst_zc": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32]),
     "yrss_dispatch_frames_zc": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "yrss_register_host_memory": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
@@ -258,7 +268,8 @@ _PROTOS = {
 }
 
 # entry points of the segmented list form (absent from older builds, see load())
-_SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists")
+_SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists", "yrss_route_dev_seg",
+              "yrss_route_seg")
 
 # include/yrss_test_hooks.h (libyrss_test.so)
 _TEST_PROTOS = {

@@ -104,6 +104,11 @@ struct ParseParams {
     uint32_t kni_enable;
     uint32_t out16;       // full output bursts as 16-byte write-through stores (0: lane-granular)
     uint32_t rank_pack;   // kCount == 2: the rank word is bucket << (ct_shift + 6) | rank
+    uint16_t route_lq;    // kCount == 4: the dispatcher lcore's own queue (yrss_route_dev_seg;
+                          // nb is then nq + 3 route buckets, see route_bucket)
+    uint16_t route_accept;   // kCount == 4: the KNI rule is "accept" (yrss_set_kni)
+                          // (the two sit in what was padding: the kernel arguments
+                          // of every variant stay where they were)
     uint32_t *tot_acc;    // kCount: per-bucket totals, added to (zeroed by the previous
                           // line scatter), or null (the scan kernel sums them)
     uint32_t *rbin;       // with tot_acc: [nb][kLbMaxWgs] counts per line-scatter range
@@ -113,6 +118,7 @@ struct ParseParams {
                           // indices grouped by bucket (yrss_dispatch_dev_seg)
     uint16_t *seg_off;    // kCount == 3: [segments][nb + 1] bucket offsets inside a segment
 };
+static_assert(sizeof(ParseParams) == 560, "route_lq / route_accept fill padding: no argument moved");
 
 struct ScatterParams {
     const int16_t *q;
@@ -341,7 +347,9 @@ struct OutSlot {
 // remainder keeps the lane-granular stores.
 // Buffer resources sized to the valid bytes drop lanes past the end, so every
 // store issues and the vmcnt bookkeeping stays exact.
-template <bool kFilter, bool kRank = false>
+// kFilterOpt (kCount == 4): the class is buffered for the route buckets but
+// P.filter may be null; a resource of no bytes then drops the stores.
+template <bool kFilter, bool kRank = false, bool kFilterOpt = false>
 __device__ __forceinline__ void flush_out(const ParseParams &P, const uint16_t *oq,
                                           const uint32_t *oh, const int8_t *of,
                                           const uint16_t *orank, uint32_t t_first,
@@ -386,8 +394,9 @@ __device__ __forceinline__ void flush_out(const ParseParams &P, const uint16_t *
         }
     }
     if (kFilter) {
-        const __amdgpu_buffer_rsrc_t rf =
-            __builtin_amdgcn_make_buffer_rsrc(P.filter + t_first, 0, (int)nv, kRsrcWord3);
+        const bool nof = kFilterOpt && !P.filter;
+        const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
+            nof ? (void *)P.q : (void *)(P.filter + t_first), 0, nof ? 0 : (int)nv, kRsrcWord3);
         for (uint32_t j = 0; j < ntiles; ++j) {
             const uint32_t e = j * kTile + lane;
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)of[e], rf, (int)e, 0, 0);
@@ -403,6 +412,25 @@ __device__ __forceinline__ void flush_out(const ParseParams &P, const uint16_t *
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane);
 
+// kCount == 4 (yrss_route_dev_seg): the packet's route class, what
+// process_packets does with it on the lcore whose queue is route_lq
+// (ff_dpdk_if.c:1058-1140), over nq + 3 buckets: b < nq, b != route_lq the
+// ring of queue b (:1087-1093); route_lq local delivery (:1137, with the
+// TRUNC / LOOP classes, as yrss_route_burst); nq freed (:1080-1083); nq + 1
+// KNI (:1132-1135); nq + 2 ARP on the local queue (:1097-1129).  Always below
+// nq + 3, whatever qv and fc hold (lanes past the batch's end, stale LDS).
+__device__ __forceinline__ uint32_t route_bucket(const ParseParams &P, int qv, int fc)
+{
+    if (qv < 0 || (uint32_t)qv >= P.nq)
+        return P.nq;
+    if ((uint32_t)qv != P.route_lq)
+        return (uint32_t)qv;
+    if (fc == kFilterArp)
+        return P.nq + 2u;
+    const bool kni = P.kni_enable && fc == (P.route_accept ? kFilterKni : kFilterUnknown);
+    return kni ? P.nq + 1u : (uint32_t)qv;
+}
+
 // kCount == 3 (yrss_dispatch_dev_seg): the finished per-queue lists of one
 // 256-packet segment, written at the chunk's flush from what the wave already
 // holds in LDS: the chunk's q and in-bucket ranks (process_tile) and its
@@ -416,9 +444,13 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane);
 // end, as in flush_out.  One byte a packet and nb + 1 offsets a segment:
 // the stand-in for the reference's per-burst enqueue into
 // dispatch_ring[port][q] (ff_dpdk_if.c:1087-1093 inside the :1674-1683 loop).
+// kRoute (kCount == 4): the buckets are the route classes, from the buffered
+// q and filter class, as process_tile counted and ranked them.
+template <bool kRoute>
 __device__ __forceinline__ void flush_seg(const ParseParams &P, const uint16_t *oq,
-                                          const uint16_t *orank, uint32_t *cnt, uint8_t *list,
-                                          uint32_t t_first, uint32_t ntiles, uint32_t lane)
+                                          const int8_t *of, const uint16_t *orank,
+                                          uint32_t *cnt, uint8_t *list, uint32_t t_first,
+                                          uint32_t ntiles, uint32_t lane)
 {
     const uint32_t nv = min(ntiles * (uint32_t)kTile, P.n - t_first);
     wave_lds_sync();
@@ -429,7 +461,8 @@ __device__ __forceinline__ void flush_seg(const ParseParams &P, const uint16_t *
     for (uint32_t j = 0; j < ntiles; ++j) {
         const uint32_t e = j * kTile + lane;
         // (lanes past the end read stale q: the bucket stays a valid lane)
-        const uint32_t bkt = bucket_of((int)(int16_t)oq[e], P.nq);
+        const uint32_t bkt = kRoute ? route_bucket(P, (int)(int16_t)oq[e], (int)of[e])
+                                    : bucket_of((int)(int16_t)oq[e], P.nq);
         const uint32_t pos = (uint32_t)__shfl((int)excl, (int)bkt, kWave) + orank[e];
         if (e < nv) {
             if (pos < nv)
@@ -595,7 +628,7 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
         // atomic returns the count before the group (a wave's LDS atomics run
         // in issue order, so tiles stay in packet order) and each lane adds
         // its position inside the group.
-        const uint32_t bkt = bucket_of(qv, P.nq);
+        const uint32_t bkt = kCount == 4 ? route_bucket(P, qv, fc) : bucket_of(qv, P.nq);
         const uint64_t peers = peer_mask(bkt, valid, P.nb);
         const uint64_t lt = lane_lt_mask(lane);
         const bool leader = valid && (peers & lt) == 0;
@@ -604,7 +637,7 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
             if (leader)
                 before = atomicAdd(&cnt[bkt], (uint32_t)__popcll(peers));
             const int ll = peers ? __builtin_ctzll(peers) : (int)lane;
-            // (kCount == 3, the segmented lists: the plain rank, no bucket tag)
+            // (kCount >= 3, the segmented lists: the plain rank, no bucket tag)
             const uint32_t tag = kCount == 2 && P.rank_pack ? bkt << (P.ct_shift + 6u) : 0u;
             ob.r[lane] = (uint16_t)(tag | (__shfl(before, ll, kWave) + (uint32_t)__popcll(peers & lt)));
         } else if (leader) {
@@ -622,6 +655,9 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
 //            and counts stay in LDS and each 4-tile chunk's finished lists
 //            leave with its q and hash (flush_seg); no rank stream, no
 //            per-chunk counts, no totals: nothing for a second kernel
+//            4: kCount == 3 over route classes (yrss_route_dev_seg, kFilter
+//            only): the bucket is route_bucket(q, filter class), not the queue;
+//            the class is computed even when no filter output is asked for
 //   kFilter  also classify protocol_filter / KNI (one byte per packet)
 //   kBlock   workgroup size (256/512): waves per CU, one key table per group
 // Window loads are non-temporal (streaming): ~25 % faster than default-policy
@@ -680,7 +716,8 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
     // check sits outside the loop: a fault-report branch inside it cost the
     // loop's load scheduling)
     bool slots_ok = true;   // (the wave still takes part in the workgroup's barriers)
-    constexpr bool kSeg = kCount == 3;   // one count slot, reused chunk after chunk
+    constexpr bool kSeg = kCount >= 3;   // one count slot, reused chunk after chunk
+    static_assert(kCount != 4 || kFilter, "route classes need the filter class");
     if (kCount && !kSeg) {
         const uint32_t own = P.nchunk > gw ? (P.nchunk - gw + W - 1u) / W : 0u;
         if (own * P.nb > kCntWords) {
@@ -708,11 +745,13 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
     };
     auto after = [&](uint32_t i, uint32_t t0, bool last) {
         if (((i + 1u) & fb_mask) == 0u || last) {
-            flush_out<kFilter, kCount == 2>(P, oq, oh, of, orank, t0 - (i & fb_mask) * kTile,
-                                            (i & fb_mask) + 1u, lane);
+            flush_out<kFilter, kCount == 2, kCount == 4>(P, oq, oh, of, orank,
+                                                         t0 - (i & fb_mask) * kTile,
+                                                         (i & fb_mask) + 1u, lane);
             if (kSeg)   // (the list: words 64..127 of the wave's count slots)
-                flush_seg(P, oq, orank, cnt_w, reinterpret_cast<uint8_t *>(cnt_w + 64),
-                          t0 - (i & fb_mask) * kTile, (i & fb_mask) + 1u, lane);
+                flush_seg<kCount == 4>(P, oq, of, orank, cnt_w,
+                                       reinterpret_cast<uint8_t *>(cnt_w + 64),
+                                       t0 - (i & fb_mask) * kTile, (i & fb_mask) + 1u, lane);
         }
     };
     constexpr int kC = kCount;
@@ -3359,9 +3398,12 @@ uint32_t resident_blocks(yrss_ctx *c, const void *fn, uint32_t block, uint32_t l
 typedef void (*ParseKernel)(ParseParams);
 
 // count: 0 none, 1 per-chunk counts, 2 counts + per-packet chunk ranks,
-// 3 segmented lists (yrss_dispatch_dev_seg only)
+// 3 segmented lists (yrss_dispatch_dev_seg only), 4 segmented lists over route
+// classes (yrss_route_dev_seg only; always with the filter class)
 ParseKernel pick_parse(int count, bool filter)
 {
+    if (count == 4)
+        return yrss_parse_hash<4, true, kParseBlock>;
     if (count == 3)
         return filter ? yrss_parse_hash<3, true, kParseBlock>
                       : yrss_parse_hash<3, false, kParseBlock>;
@@ -4374,14 +4416,19 @@ int yrss_dispatch_dev(yrss_ctx *c, const uint8_t *d_win, uint32_t win_stride,
 // touches none of the compaction workspace (no ranks, counts or totals), so
 // it may sit between two yrss_dispatch_dev batches; it keeps their stream
 // rules because it shares the context's fault record and timing events.
-int yrss_dispatch_dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, void *stream)
+// route (yrss_route_dev_seg): the kCount == 4 variant instead, its buckets the
+// nb_queues + 3 route classes of the lcore whose queue is queue_id, under the
+// KNI state as yrss_set_kni last left it; the same checks, launch and limits.
+static int dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, bool route,
+                   uint16_t queue_id, void *stream)
 {
     if (!c || !b)
         return -EINVAL;
     if (c->pend.active)      // the host burst in flight owns the context
         return -EBUSY;
     const uint32_t n = b->n;
-    if (c->nb > YRSS_SEG_MAX_BUCKETS)
+    const uint32_t nbk = route ? c->nb + 2u : c->nb;
+    if (nbk > YRSS_SEG_MAX_BUCKETS)
         return -ENOTSUP;
     if (b->win_stride < YRSS_WIN_MIN || (b->win_stride & 15u) || n > YRSS_SEG_MAX_BATCH)
         return -EINVAL;
@@ -4405,7 +4452,8 @@ int yrss_dispatch_dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, void 
     }
     c->last_stream = s;
     c->last_stream_valid = true;
-    const bool filter = b->filter != nullptr;
+    // (the route classes need the filter class whether or not it is stored)
+    const bool filter = route || b->filter != nullptr;
     ParseParams P = c->proto;
     P.win = b->win;
     P.len = b->len;
@@ -4416,6 +4464,9 @@ int yrss_dispatch_dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, void 
     P.fault = c->d_fault_rec;
     P.n = n;
     P.stride = b->win_stride;
+    P.nb = nbk;
+    P.route_lq = queue_id;
+    P.route_accept = c->kni_accept ? 1 : 0;
     // a chunk is a segment: 4 tiles, the parse kernel's output burst
     // (yrss_tuning.chunk_tiles does not apply)
     static_assert(YRSS_SEG_PKTS == kOutTiles * kTile, "a segment is one output burst");
@@ -4437,11 +4488,25 @@ int yrss_dispatch_dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, void 
     P.seg_off = b->seg_off;
     {
         Timed t(c, YRSS_K_PARSE_HASH);
-        hipExtLaunchKernelGGL(pick_parse(3, filter), dim3(grid_for(c, n)), dim3(kParseBlock),
-                              (uint32_t)parse_lds(filter), s, t.a, t.b, 0, P);
+        hipExtLaunchKernelGGL(pick_parse(route ? 4 : 3, filter), dim3(grid_for(c, n)),
+                              dim3(kParseBlock), (uint32_t)parse_lds(filter), s, t.a, t.b, 0, P);
     }
     YRSS_HIP(hipGetLastError());
     return 0;
+}
+
+int yrss_dispatch_dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, void *stream)
+{
+    return dev_seg(c, b, false, 0, stream);
+}
+
+int yrss_route_dev_seg(yrss_ctx *c, const struct yrss_dev_route_batch *b, void *stream)
+{
+    if (!b)
+        return -EINVAL;
+    const struct yrss_dev_seg_batch sb = {b->win, b->win_stride, b->n,       b->len,    b->q,
+                                          b->hash, b->filter,    b->seg_idx, b->seg_off};
+    return dev_seg(c, &sb, true, b->queue_id, stream);
 }
 
 int yrss_dispatch_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len,

@@ -9,8 +9,14 @@
 // arrays come from a device buffer the caller may have mis-sized or not yet
 // synchronised, so nothing read from them is used as an index before it is
 // checked.  yastack_amd/segments.py is the Python twin.
+//
+// yrss_route_seg consumes the routed form of yrss_route_dev_seg (nb_queues + 3
+// route buckets a segment) and performs process_packets' hand-off
+// (ff_dpdk_if.c:1058-1140) with list walks alone: what yrss_route_burst decides
+// per packet from q and filter, the parse kernel has already decided.
 #include <errno.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "yrss.h"
 
@@ -56,6 +62,134 @@ int yrss_seg_to_lists(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t 
                 out_qidx[w++] = s * YRSS_SEG_PKTS + idx[k];
             }
             done[b] += (uint32_t)(o[b + 1] - o[b]);
+        }
+    }
+    return 0;
+}
+
+// Every offset row 0 .. len_s and monotone, every index byte below len_s and
+// (a packet handed off twice would be freed twice) present once in its segment.
+static int route_seg_valid(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
+                           uint32_t nq, bool local_ok)
+{
+    const uint32_t nrb = nq + 3u;
+    const uint32_t nseg = n / YRSS_SEG_PKTS + (n % YRSS_SEG_PKTS ? 1u : 0u);
+    for (uint32_t s = 0; s < nseg; ++s) {
+        const uint16_t *o = seg_off + (size_t)s * (nrb + 1u);
+        const uint8_t *idx = seg_idx + (size_t)s * YRSS_SEG_PKTS;
+        const uint32_t len = n - s * YRSS_SEG_PKTS < YRSS_SEG_PKTS ? n - s * YRSS_SEG_PKTS
+                                                                   : (uint32_t)YRSS_SEG_PKTS;
+        if (o[0] != 0 || o[nrb] != len)
+            return -EINVAL;
+        for (uint32_t b = 0; b < nrb; ++b)
+            if (o[b + 1] < o[b])
+                return -EINVAL;
+        // no local queue: nothing can be KNI or local ARP
+        if (!local_ok && o[nq + 1u] != len)
+            return -EINVAL;
+        uint64_t seen[YRSS_SEG_PKTS / 64] = {0};
+        for (uint32_t k = 0; k < len; ++k) {
+            const uint32_t i = idx[k];
+            if (i >= len || (seen[i >> 6] >> (i & 63u)) & 1u)
+                return -EINVAL;
+            seen[i >> 6] |= 1ull << (i & 63u);
+        }
+    }
+    return 0;
+}
+
+int yrss_route_seg(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
+                   uint16_t nb_queues, uint16_t queue_id, int kni_clone, const int8_t *filter,
+                   void *const *objs, const struct yrss_route_ops *ops, void **out_local,
+                   void **out_kni, struct yrss_route_result *res)
+{
+    if (!ops || !ops->enqueue || !ops->clone || !ops->release || !res)
+        return -EINVAL;
+    if (nb_queues < 1 || nb_queues > YRSS_ROUTE_SEG_MAX_QUEUES)
+        return -EINVAL;
+    if (n && (!seg_idx || !seg_off || !objs || !out_local || !out_kni))
+        return -EINVAL;
+    const uint32_t nq = nb_queues, nrb = nq + 3u;
+    const bool local_ok = queue_id < nq;
+    memset(res, 0, sizeof(*res));
+    if (route_seg_valid(seg_idx, seg_off, n, nq, local_ok))
+        return -EINVAL;
+    const uint32_t nseg = n / YRSS_SEG_PKTS + (n % YRSS_SEG_PKTS ? 1u : 0u);
+    for (uint32_t s = 0; s < nseg; ++s) {
+        const uint16_t *o = seg_off + (size_t)s * (nrb + 1u);
+        const uint8_t *idx = seg_idx + (size_t)s * YRSS_SEG_PKTS;
+        void *const *m = objs + (size_t)s * YRSS_SEG_PKTS;
+        // ARP kept on this lcore is deep-cloned to every other queue, in packet
+        // order, queue order inside a packet, then once more for KNI
+        // (ff_dpdk_if.c:1099-1129)
+        const uint8_t *arp = idx + o[nq + 2u];
+        const uint32_t na = (uint32_t)(o[nq + 3u] - o[nq + 2u]);
+        void *cl[YRSS_SEG_PKTS][YRSS_ROUTE_SEG_MAX_QUEUES];
+        void *kc[YRSS_SEG_PKTS];
+        for (uint32_t a = 0; a < na; ++a) {
+            for (uint16_t j = 0; j < nq; ++j)
+                cl[a][j] = j != queue_id ? ops->clone(ops->user, m[arp[a]], j) : nullptr;
+            kc[a] = kni_clone ? ops->clone(ops->user, m[arp[a]], 0xFFFFu) : nullptr;
+        }
+        // one FIFO burst per ring: bucket j merged by packet index with the
+        // clones for j (a failed clone enqueues nothing, :1114-1118)
+        void *burst[YRSS_SEG_PKTS];
+        for (uint16_t j = 0; j < nq; ++j) {
+            if (j == queue_id)
+                continue;
+            uint32_t k = o[j], nb = 0, a = 0;
+            const uint32_t e = o[j + 1];
+            while (k < e || a < na) {
+                if (a < na && (k >= e || arp[a] < idx[k])) {
+                    if (cl[a][j])
+                        burst[nb++] = cl[a][j];
+                    ++a;
+                } else {
+                    burst[nb++] = m[idx[k++]];
+                }
+            }
+            unsigned done = nb ? ops->enqueue(ops->user, j, burst, nb) : 0u;
+            if (done > nb)
+                done = nb;
+            res->n_ring[j] += done;
+            for (uint32_t r = done; r < nb; ++r) {      // ring full: free (:1090)
+                ops->release(ops->user, burst[r]);
+                res->n_freed++;
+            }
+        }
+        // ret < 0 || ret >= nb_queues: freed (:1080-1083)
+        for (uint32_t k = o[nq]; k < o[nq + 1u]; ++k) {
+            ops->release(ops->user, m[idx[k]]);
+            res->n_freed++;
+        }
+        if (!local_ok)
+            continue;
+        // local input, in packet order: the local bucket and the ARP packets
+        uint32_t k = o[queue_id], a = 0;
+        const uint32_t e = o[queue_id + 1u];
+        while (k < e || a < na) {
+            if (a < na && (k >= e || arp[a] < idx[k])) {
+                out_local[res->n_local++] = m[arp[a++]];
+                res->n_arp++;
+            } else {
+                const uint32_t i = s * YRSS_SEG_PKTS + idx[k++];
+                if (filter && (filter[i] == YRSS_FILTER_TRUNC || filter[i] == YRSS_FILTER_LOOP))
+                    res->n_unresolved++;
+                out_local[res->n_local++] = objs[i];
+            }
+        }
+        // ff_kni_enqueue, in packet order: the KNI bucket and the KNI clones
+        k = o[nq + 1u];
+        a = 0;
+        const uint32_t ek = o[nq + 2u];
+        while (k < ek || a < na) {
+            if (a < na && (k >= ek || arp[a] < idx[k])) {
+                if (kc[a])
+                    out_kni[res->n_kni++] = kc[a];
+                ++a;
+            } else {
+                out_kni[res->n_kni++] = m[idx[k++]];
+            }
         }
     }
     return 0;

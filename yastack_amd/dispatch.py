@@ -58,6 +58,9 @@ class SegResult:
     ``seg_idx``   n x uint8: bytes [256 s, 256 s + len_s) are segment s's
                   segment-local packet indices, grouped by bucket, FIFO inside
     ``seg_off``   nseg x (nb_queues + 2) uint16 offsets into those bytes
+
+    From ``yrss_route_dev_seg`` the buckets are the nb_queues + 3 route classes
+    (``segments.route_buckets``) and a ``seg_off`` row has nb_queues + 4 entries.
     """
 
     q: object
@@ -100,8 +103,10 @@ def _check_dev_sizes(n, stride, win, lens, out, nb_queues):
             raise ValueError(f"{name} holds {nbytes(t)} bytes, the batch of {n} needs {b}")
 
 
-def _check_seg_sizes(n, stride, win, lens, out, nb_queues):
-    """As _check_dev_sizes, for the segmented form's buffers."""
+def _check_seg_sizes(n, stride, win, lens, out, nb_queues, nbk=None):
+    """As _check_dev_sizes, for the segmented form's buffers (nbk buckets a
+    segment: nb_queues + 1, or the routed form's nb_queues + 3)."""
+    nbk = nb_queues + 1 if nbk is None else nbk
     def nbytes(t):
         return 0 if t is None else int(t.numel()) * int(t.element_size())
     if n < 0:
@@ -110,7 +115,7 @@ def _check_seg_sizes(n, stride, win, lens, out, nb_queues):
         return
     nseg = -(-n // abi.SEG_PKTS)
     need = [("win", win, n * stride), ("lens", lens, 2 * n), ("q", out.q, 2 * n),
-            ("seg_idx", out.seg_idx, n), ("seg_off", out.seg_off, 2 * nseg * (nb_queues + 2))]
+            ("seg_idx", out.seg_idx, n), ("seg_off", out.seg_off, 2 * nseg * (nbk + 1))]
     if out.hash is not None:
         need.append(("hash", out.hash, 4 * n))
     if out.filter is not None:
@@ -155,6 +160,7 @@ class SoftRss:
         ctx = ctypes.c_void_p()
         abi.check(self._lib.yrss_init(ctypes.byref(cfg), ctypes.byref(ctx)), "yrss_init")
         self._ctx = ctx
+        self._kni_enable = False
 
     @classmethod
     def from_ff_config(cls, path: str, port: int = 0, device: int = 0, **kw) -> "SoftRss":
@@ -219,6 +225,7 @@ class SoftRss:
         enc = (lambda x: None if x is None else x.encode())
         abi.check(self._lib.yrss_set_kni(self._ctx, 1 if enable else 0, enc(method),
                                          enc(tcp_ports), enc(udp_ports)), "yrss_set_kni")
+        self._kni_enable = bool(enable)
 
     # -- device-resident path ---------------------------------------------
     def dispatch_dev(self, win, lens, stride: int, n: int | None = None, *,
@@ -262,6 +269,34 @@ class SoftRss:
         si = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
         so = torch.empty((nseg, self.nb_queues + 2), dtype=torch.int16, device=dev)
         return SegResult(q, h, f, si, so, n)
+
+    def route_dev_seg(self, win, lens, stride: int, queue_id: int, n: int | None = None, *,
+                      out=None, want_hash: bool = True, want_filter: bool = False,
+                      stream=None) -> SegResult:
+        """Classify n packets resident in HBM into process_packets' hand-off
+        classes for the lcore whose queue is ``queue_id`` and return them as
+        segmented lists over nb_queues + 3 route buckets (``yrss_route_dev_seg``:
+        one launch; nb_queues <= 13, n <= 2^24; the KNI state is that of the
+        last :meth:`set_kni`).  :meth:`route_seg` performs the hand-off."""
+        n = int(lens.numel()) if n is None else n
+        if out is None:
+            out = self.alloc_route_out(n, lens.device, want_hash, want_filter)
+        _check_seg_sizes(n, stride, win, lens, out, self.nb_queues, self.nb_queues + 3)
+        b = abi.DevRouteBatch(_ptr(win), stride, n, _ptr(lens), _ptr(out.q), _ptr(out.hash),
+                              _ptr(out.filter), _ptr(out.seg_idx), _ptr(out.seg_off), queue_id)
+        rc = self._lib.yrss_route_dev_seg(self._ctx, ctypes.byref(b), self._stream(stream))
+        abi.check(rc, "yrss_route_dev_seg")
+        out.n = n
+        return out
+
+    def alloc_route_out(self, n: int, dev, want_hash=True, want_filter=False) -> SegResult:
+        """Output buffers of :meth:`route_dev_seg`: those of the segmented form
+        with nb_queues + 4 offsets a segment."""
+        torch = self._torch()
+        out = self.alloc_seg_out(n, dev, want_hash, want_filter)
+        nseg = max(-(-n // abi.SEG_PKTS), 1)
+        out.seg_off = torch.empty((nseg, self.nb_queues + 4), dtype=torch.int16, device=dev)
+        return out
 
     def alloc_out(self, n: int, dev, want_hash=True, compact=True,
                   want_filter=False) -> DispatchResult:
@@ -472,6 +507,54 @@ class SoftRss:
                                         ctypes.byref(ops), _ptr(local), _ptr(kni),
                                         ctypes.byref(res))
         abi.check(rc, "yrss_route_burst")
+        return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
+
+    def route_seg(self, result_or_arrays, objs, queue_id: int, enqueue, clone, release,
+                  kni_primary: bool = True):
+        """process_packets' hand-off from routed segments (``yrss_route_seg``),
+        mirroring :meth:`route_burst`: ``result_or_arrays`` is the SegResult of
+        :meth:`route_dev_seg` (copied to the host here; synchronise its stream
+        first) or host arrays ``(seg_idx, seg_off, n)`` / ``(seg_idx, seg_off,
+        n, filter)``; ``objs`` the n mbuf addresses, ``queue_id`` the one the
+        lists were built for.  Returns (local list, kni list, RouteResult)."""
+        if isinstance(result_or_arrays, SegResult):
+            r = result_or_arrays
+            n = int(r.n)
+            host = (lambda t: None if t is None else t.cpu().numpy())
+            seg_idx, seg_off, filt = host(r.seg_idx), host(r.seg_off), host(r.filter)
+        else:
+            seg_idx, seg_off, n, *rest = result_or_arrays
+            filt = rest[0] if rest else None
+            n = int(n)
+        nseg = -(-n // abi.SEG_PKTS)
+        seg_idx = np.ascontiguousarray(np.asarray(seg_idx).reshape(-1)).view(np.uint8)
+        seg_off = np.ascontiguousarray(np.asarray(seg_off).reshape(-1)).view(np.uint16)
+        mb = np.ascontiguousarray(objs, dtype=np.uint64)
+        if filt is not None:
+            filt = np.ascontiguousarray(np.asarray(filt).reshape(-1)).view(np.int8)
+        # the C call sees raw pointers only: the sizes are checked here
+        if seg_idx.size < n or seg_off.size < nseg * (self.nb_queues + 4) or mb.size < n or \
+                (filt is not None and filt.size < n):
+            raise ValueError("arrays shorter than the batch")
+
+        def _enq(user, queue, ptrs, cnt):
+            return int(enqueue(int(queue), [int(ptrs[i] or 0) for i in range(cnt)]))
+
+        def _clone(user, m, queue):
+            return int(clone(int(m or 0), int(queue)) or 0)
+
+        def _rel(user, m):
+            release(int(m or 0))
+
+        ops = abi.RouteOps(abi.ENQUEUE_FN(_enq), abi.CLONE_FN(_clone), abi.RELEASE_FN(_rel), None)
+        local = np.zeros(max(n, 1), np.uint64)
+        kni = np.zeros(max(n, 1), np.uint64)
+        res = abi.RouteResult()
+        rc = self._lib.yrss_route_seg(_ptr(seg_idx), _ptr(seg_off), n, self.nb_queues, queue_id,
+                                      1 if self._kni_enable and kni_primary else 0, _ptr(filt),
+                                      _ptr(mb), ctypes.byref(ops), _ptr(local), _ptr(kni),
+                                      ctypes.byref(res))
+        abi.check(rc, "yrss_route_seg")
         return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
 
     # -- connect-side RSS check (ff_rss_check) -------------------------------

@@ -13,6 +13,11 @@ reference's per-burst enqueue into dispatch_ring[port][q] (:1087-1093 inside the
 :1674-1683 loop).  :func:`from_q` builds the form from a per-packet queue array
 (the tests' expected value, from the oracle's q); :func:`to_lists` is the numpy
 twin of the C helper ``yrss_seg_to_lists``; :func:`to_lists_c` calls that helper.
+
+The routed form of ``yrss_route_dev_seg`` is the same layout over nrb =
+nb_queues + 3 route buckets (:func:`route_buckets`: what process_packets,
+:1058-1140, does with the packet on the lcore whose queue is ``queue_id``);
+:func:`route_from` builds it from per-packet q and filter-class arrays.
 """
 from __future__ import annotations
 
@@ -36,20 +41,53 @@ def buckets_of(q: np.ndarray, nb_queues: int) -> np.ndarray:
     return np.where((q >= 0) & (q < nb_queues), q, nb_queues)
 
 
-def from_q(q: np.ndarray, nb_queues: int):
-    """(seg_idx uint8[n], seg_off uint16[nseg, nb_queues + 2]) of a q array."""
-    n = int(np.asarray(q).size)
-    nbk = nb_queues + 1
+def from_buckets(bkt: np.ndarray, nb: int):
+    """(seg_idx uint8[n], seg_off uint16[nseg, nb + 1]) of a per-packet bucket
+    array with values in [0, nb)."""
+    bkt = np.asarray(bkt).astype(np.int64).reshape(-1)
+    n = int(bkt.size)
+    if n and (bkt.min() < 0 or bkt.max() >= nb):
+        raise ValueError("bucket out of range")
     nseg = nseg_for(n)
-    bkt = buckets_of(q, nb_queues)
     seg_idx = np.empty(n, np.uint8)
-    seg_off = np.zeros((nseg, nbk + 1), np.uint16)
+    seg_off = np.zeros((nseg, nb + 1), np.uint16)
     for s in range(nseg):
         b = bkt[s * SEG:(s + 1) * SEG]
         # a stable sort by bucket keeps packet order inside each bucket
         seg_idx[s * SEG:s * SEG + b.size] = np.argsort(b, kind="stable")
-        seg_off[s, 1:] = np.cumsum(np.bincount(b, minlength=nbk))
+        seg_off[s, 1:] = np.cumsum(np.bincount(b, minlength=nb))
     return seg_idx, seg_off
+
+
+def from_q(q: np.ndarray, nb_queues: int):
+    """(seg_idx uint8[n], seg_off uint16[nseg, nb_queues + 2]) of a q array."""
+    return from_buckets(buckets_of(q, nb_queues), nb_queues + 1)
+
+
+def route_buckets(q: np.ndarray, fclass: np.ndarray, nb_queues: int, queue_id: int,
+                  kni_enable: bool, kni_accept: bool) -> np.ndarray:
+    """Route bucket of every packet (``yrss_route_dev_seg``), nq = nb_queues:
+    b < nq, b != queue_id the ring of queue b; queue_id local delivery (with
+    the TRUNC / LOOP classes); nq freed; nq + 1 KNI; nq + 2 ARP on the local
+    queue.  queue_id >= nq: no packet is local."""
+    q = np.asarray(q).astype(np.int64)
+    f = np.asarray(fclass).astype(np.int64)
+    nq = int(nb_queues)
+    bkt = np.where((q >= 0) & (q < nq), q, nq)
+    local = bkt == queue_id if queue_id < nq else np.zeros(q.shape, bool)
+    arp = local & (f == abi.FILTER_ARP)
+    want = abi.FILTER_KNI if kni_accept else abi.FILTER_UNKNOWN
+    kni = local & ~arp & bool(kni_enable) & (f == want)
+    bkt = np.where(kni, nq + 1, bkt)
+    return np.where(arp, nq + 2, bkt)
+
+
+def route_from(q: np.ndarray, fclass: np.ndarray, nb_queues: int, queue_id: int,
+               kni_enable: bool, kni_accept: bool):
+    """(seg_idx uint8[n], seg_off uint16[nseg, nb_queues + 4]): the routed
+    segmented lists of per-packet q and filter-class arrays."""
+    return from_buckets(route_buckets(q, fclass, nb_queues, queue_id, kni_enable, kni_accept),
+                        nb_queues + 3)
 
 
 def to_lists(seg_idx: np.ndarray, seg_off: np.ndarray, n: int, nbk: int):

@@ -178,7 +178,9 @@ int yrss_dispatch_dev(yrss_ctx *ctx, const uint8_t *d_win, uint32_t win_stride,
  * ff_dpdk_kni.c:99-118,300-331): enable, method "accept"/"reject" (anything
  * else is rejected like ff_config.c:548-553), and comma/range port lists
  * ("80,443,8000-8080") parsed with kni_set_bitmap's rules into the 8 KiB
- * htons-indexed bitmaps.  NULL lists leave a bitmap empty. */
+ * htons-indexed bitmaps.  NULL lists leave a bitmap empty.  On a context with
+ * a route worker (yrss_worker_start_route): -EBUSY while a burst is pending,
+ * otherwise the worker is halted and relaunched by the next submit. */
 int yrss_set_kni(yrss_ctx *ctx, int enable, const char *method,
                  const char *tcp_ports, const char *udp_ports);
 
@@ -335,6 +337,49 @@ int yrss_route_seg(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
                    const struct yrss_route_ops *ops, void **out_local, void **out_kni,
                    struct yrss_route_result *res);
 
+/* ---- routed global lists: the same classes for one-workgroup bursts ----------- */
+
+/* The host bursts (one launch of the one-workgroup burst kernel, n <= 4096) and
+ * the persistent worker build global lists, not segments: 32-bit packet
+ * indices and one offset row.  Their routed form is
+ *   ridx     n x uint32 packet indices grouped by route class, FIFO inside
+ *   rstart   nb_queues + 4 x uint32 offsets: class b = ridx[rstart[b] ..
+ *            rstart[b+1]), rstart[0] == 0, rstart[nb_queues + 3] == n
+ * with the classes numbered exactly as in yrss_route_dev_seg above.  One lane
+ * holds one class, so nb_queues + 3 <= 64. */
+#define YRSS_ROUTE_LISTS_MAX_QUEUES 61
+
+/* Synchronous: a host gather and ONE launch, like yrss_dispatch_burst /
+ * yrss_dispatch_frames (flags: YRSS_F_WRITE_RSS; YRSS_F_ASYNC is refused with
+ * -EINVAL).  out_hash and out_filter may be NULL (the classes are computed
+ * either way); out_q, out_ridx and out_rstart are required.  n == 0 zeroes the
+ * nb_queues + 4 offsets.  -ENOTSUP, before anything is launched, for n > 4096
+ * or nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES: larger batches belong to
+ * yrss_route_dev_seg.  The KNI state is the one yrss_set_kni last set. */
+int yrss_route_lists_burst(yrss_ctx *ctx, void *const *mbufs, uint32_t n, uint16_t queue_id,
+                           int16_t *out_q, uint32_t *out_hash, int8_t *out_filter,
+                           uint32_t *out_ridx, uint32_t *out_rstart, uint32_t flags);
+int yrss_route_lists_frames(yrss_ctx *ctx, const uint8_t *const *data, const uint16_t *len,
+                            uint32_t n, uint16_t queue_id, int16_t *out_q, uint32_t *out_hash,
+                            int8_t *out_filter, uint32_t *out_ridx, uint32_t *out_rstart);
+
+/* Host-only: process_packets' hand-off from routed global lists; the twin of
+ * yrss_route_seg for one burst, with its arguments, callbacks and results
+ * (kni_primary is its kni_clone: pass "KNI on && kni_primary").  What
+ * yrss_route_burst does per packet from q and filter, done by list walks:
+ * ARP clones in packet order (queue order inside a packet, then the KNI
+ * clone), one enqueue per ring merged by index with the successful clones,
+ * release of the refused tail and of the freed class, out_local = local class
+ * merged with the ARP class, out_kni = KNI class merged with the KNI clones.
+ * n_unresolved is 0 without filter.  Validated before the first callback, a
+ * failure returning -EINVAL with no callback made: the offsets monotone from 0
+ * to n, every index < n and present exactly once, the KNI and ARP classes empty
+ * when queue_id >= nb_queues, nb_queues <= YRSS_ROUTE_LISTS_MAX_QUEUES. */
+int yrss_route_lists(const uint32_t *ridx, const uint32_t *rstart, uint32_t n,
+                     uint16_t nb_queues, uint16_t queue_id, int kni_primary,
+                     const int8_t *filter, void *const *objs,
+                     const struct yrss_route_ops *ops, void **out_local, void **out_kni,
+                     struct yrss_route_result *res);
 
 /* ---- host-resident dispatch (the drop-in burst hook) ------------------------ */
 
@@ -590,6 +635,20 @@ int yrss_timing_quantile(yrss_ctx *ctx, int kernel, double q, double *ms);
 #define YRSS_WORKER_MAX_BLOCKS 128
 #define YRSS_WORKER_MAX_SLOTS 4096
 int yrss_worker_start(yrss_ctx *ctx, uint32_t nslots, uint32_t nblocks);
+/* The same worker in route mode, for the lcore whose queue is queue_id
+ * (queue_id >= nb_queues is legal: nothing is local): the three submit calls
+ * keep their signatures, out_q and out_hash are unchanged, and out_qidx /
+ * out_qstart receive the ROUTED lists of yrss_route_lists_burst: packet indices
+ * grouped by route class, FIFO inside a class, and nb_queues + 4 offsets
+ * (n == 0 zeroes them), for yrss_route_lists to hand off.  YRSS_F_WRITE_RSS,
+ * the frames form and the windows form work as in the plain worker; there is
+ * no per-packet filter output.  Same arguments and limits as
+ * yrss_worker_start; -ENOTSUP when nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES.
+ * The KNI state is the context's when the kernel is launched: yrss_set_kni on
+ * a context with a route worker returns -EBUSY while a burst is pending, and
+ * otherwise halts the kernel, so the next submit relaunches it with the new
+ * state (as registering host memory does). */
+int yrss_worker_start_route(yrss_ctx *ctx, uint32_t nslots, uint32_t nblocks, uint16_t queue_id);
 /* Queue one burst (n <= YRSS_WORKER_MAX_BURST; flags: YRSS_F_WRITE_RSS);
  * *ticket identifies it for yrss_worker_poll.  The output arrays must stay
  * valid until the ticket is polled. */

@@ -35,6 +35,9 @@ SEG_MAX_BUCKETS = 16
 SEG_MAX_BATCH = 1 << 24
 # routed segmented lists (yrss_route_dev_seg): nb_queues + 3 route buckets
 ROUTE_SEG_MAX_QUEUES = 13
+# routed global lists of one-workgroup bursts (yrss_route_lists_*, the route
+# worker): one lane per class, nb_queues + 3 <= 64
+ROUTE_LISTS_MAX_QUEUES = 61
 F_WRITE_RSS = 0x1
 F_ASYNC = 0x2
 
@@ -218,6 +221,7 @@ _PROTOS = {
                                                  ctypes.POINTER(ctypes.c_uint64)]),
     "yrss_worker_submit_windows": (ctypes.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
                                                   ctypes.POINTER(ctypes.c_uint64)]),
+    "yrss_worker_start_route": (ctypes.c_int, [_vp, _u32, _u32, ctypes.c_uint16]),
     "yrss_worker_poll": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_int]),
     "yrss_worker_stop": (ctypes.c_int, [_vp]),
     "yrss_dispatch_frames_zc_ex": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
@@ -251,6 +255,13 @@ _PROTOS = {
     "yrss_route_seg": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_uint16, ctypes.c_uint16,
                                       ctypes.c_int, _vp, _vp, ctypes.POINTER(RouteOps), _vp, _vp,
                                       ctypes.POINTER(RouteResult)]),
+    "yrss_route_lists_burst": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_uint16, _vp, _vp, _vp,
+                                              _vp, _vp, _u32]),
+    "yrss_route_lists_frames": (ctypes.c_int, [_vp, _vp, _vp, _u32, ctypes.c_uint16, _vp, _vp,
+                                               _vp, _vp, _vp]),
+    "yrss_route_lists": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_uint16, ctypes.c_uint16,
+                                        ctypes.c_int, _vp, _vp, ctypes.POINTER(RouteOps), _vp, _vp,
+                                        ctypes.POINTER(RouteResult)]),
     "yrss_dispatch_burst_zc": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32]),
     "yrss_dispatch_frames_zc": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "yrss_register_host_memory": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
@@ -269,7 +280,8 @@ _PROTOS = {
 
 # entry points of the segmented list form (absent from older builds, see load())
 _SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists", "yrss_route_dev_seg",
-              "yrss_route_seg")
+              "yrss_route_seg", "yrss_worker_start_route", "yrss_route_lists_burst",
+              "yrss_route_lists_frames", "yrss_route_lists")
 
 # include/yrss_test_hooks.h (libyrss_test.so)
 _TEST_PROTOS = {

@@ -2565,7 +2565,7 @@ struct SmallParams {
     uint64_t seq;        // stored into *done once every output is visible to the host
 };
 
-__host__ __device__ inline size_t small_lds(uint32_t nb, bool filter)
+__host__ __device__ constexpr size_t small_lds(uint32_t nb, bool filter)
 {
     return kTblBytes + kSmallWaves * (kStageBytes + kOutBytes) +
            (size_t)(kSmallTiles * nb + kSmallMaxNb) * sizeof(uint32_t) +
@@ -2624,7 +2624,14 @@ struct BurstIO {
     uint64_t seq;        // stored into *done once every output is visible to the host
 };
 
-template <bool kFilter, uint32_t kTW = kOutTiles>   // kTW: tiles per wave (n <= kTW * 1024)
+// kRoute (yrss_route_lists_*, yrss_worker_start_route; kFilter only): the
+// buckets are the P.nb = nq + 3 route classes of route_bucket(), counted and
+// ranked by process_tile<4> and placed from the buffered q and filter class;
+// the class is computed whether or not P.filter stores it.  The lists are
+// global (one start row, 32-bit indices): no segment, so the only limit is one
+// lane per class, nq + 3 <= 64.
+template <bool kFilter, uint32_t kTW = kOutTiles,   // kTW: tiles per wave (n <= kTW * 1024)
+          bool kRoute = false>
 __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, const GatherIO &gio,
                                  const BurstIO &S, const SmallLds &L, uint32_t wave,
                                  uint32_t lane)
@@ -2654,7 +2661,9 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
         const uint32_t t = wave + j * kSmallWaves;
         if (t >= ntiles)
             break;
-        process_tile<2, kFilter>(P, L.tbl, L.kni, L.stage, L.cnt + t * P.nb,
+        static_assert(!kRoute || kFilter, "route classes need the filter class");
+        // (kCount 4 is kCount 2 without the rank tag, over route_bucket)
+        process_tile<kRoute ? 4 : 2, kFilter>(P, L.tbl, L.kni, L.stage, L.cnt + t * P.nb,
                                  OutSlot{L.oq + j * kTile, L.oh + j * kTile, L.of + j * kTile,
                                          L.orank + j * kTile},
                                  t * kTile, P.n, lane, r[j], Ln[j]);
@@ -2688,12 +2697,16 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
         const uint32_t t = wave + j * kSmallWaves;
         if (t >= ntiles)
             break;
-        flush_out<kFilter>(P, L.oq + j * kTile, L.oh + j * kTile, L.of + j * kTile,
-                           L.orank + j * kTile, t * kTile, 1u, lane);
+        flush_out<kFilter, false, kRoute>(P, L.oq + j * kTile, L.oh + j * kTile,
+                                          L.of + j * kTile, L.orank + j * kTile, t * kTile, 1u,
+                                          lane);
         const uint32_t pkt = t * kTile + lane;
         if (pkt < P.n) {
             if (S.qidx) {
-                const uint32_t b = bucket_of((int16_t)L.oq[j * kTile + lane], P.nq);
+                const uint32_t b =
+                    kRoute ? route_bucket(P, (int)(int16_t)L.oq[j * kTile + lane],
+                                          (int)L.of[j * kTile + lane])
+                           : bucket_of((int16_t)L.oq[j * kTile + lane], P.nq);
                 const uint32_t d = L.start[b] + L.cnt[t * P.nb + b] + L.orank[j * kTile + lane];
                 if (d < P.n)
                     S.qidx[d] = pkt;
@@ -2711,16 +2724,16 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
     }
 }
 
-template <bool kFilter>
+template <bool kFilter, bool kRoute = false>
 __global__ __launch_bounds__(kSmallBlock) void yrss_burst_small(SmallParams S)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const SmallLds L = small_carve(smem, wave, S.P.nb);
     small_tables<kFilter>(S.P, L);
-    small_burst_body<kFilter>(S.P, S.G, gather_io(S.G),
-                              BurstIO{S.qidx, S.qstart, S.gather, S.writeback}, L, wave,
-                              lane_id());
+    small_burst_body<kFilter, kOutTiles, kRoute>(S.P, S.G, gather_io(S.G),
+                                                 BurstIO{S.qidx, S.qstart, S.gather, S.writeback},
+                                                 L, wave, lane_id());
     if (S.done) {
         // the host spins on this word instead of a stream synchronisation:
         // every wave's stores drained, one system-scope release, then the word
@@ -2822,19 +2835,30 @@ struct WorkerParams {
 };
 
 // small_burst_body's LDS, then 64 B of control words, then the output-address
-// cache: kWorkerOutCache slots x 4 addresses and one valid word per slot
-size_t worker_lds(uint32_t nb)
+// cache: kWorkerOutCache slots x 4 addresses and one valid word per slot.
+// route: the KNI bitmaps sit in LDS too (16 KiB, built once per launch) and
+// nb is nq + 3; at the cap of 64 classes that is 148928 of the CU's 160 KiB.
+constexpr size_t worker_lds(uint32_t nb, bool route = false)
 {
-    return small_lds(nb, false) + 64u + kWorkerOutCache * (32u + 4u);
+    return small_lds(nb, route) + 64u + kWorkerOutCache * (32u + 4u);
 }
+static_assert(worker_lds(YRSS_ROUTE_LISTS_MAX_QUEUES + 3u, true) <= 160u * 1024u &&
+                  YRSS_ROUTE_LISTS_MAX_QUEUES + 3u <= kSmallMaxNb,
+              "the route worker's LDS at the most classes fits one CU");
 
+// kRoute (yrss_worker_start_route): W.P.nb is nq + 3 and the lists the slot's
+// qidx / qstart addresses receive are the routed ones (nq + 4 offsets), under
+// W.P.route_lq / route_accept / kni_enable as the context held them at launch.
+// WorkerSlot has no room for a filter address: the class is computed, never
+// stored.
+template <bool kRoute>
 __global__ __launch_bounds__(kSmallBlock) void yrss_burst_worker(WorkerParams W)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t lane = lane_id();
     const SmallLds L = small_carve(smem, wave, W.P.nb);
-    uint32_t *ctl = reinterpret_cast<uint32_t *>(smem + small_lds(W.P.nb, false));
+    uint32_t *ctl = reinterpret_cast<uint32_t *>(smem + small_lds(W.P.nb, kRoute));
     uint64_t *ocache = reinterpret_cast<uint64_t *>(ctl + 16);
     uint32_t *ovalid = reinterpret_cast<uint32_t *>(ocache + 4 * kWorkerOutCache);
     // slots of this workgroup: slot of ticket t is t mod nslots, and the
@@ -2842,7 +2866,7 @@ __global__ __launch_bounds__(kSmallBlock) void yrss_burst_worker(WorkerParams W)
     const uint32_t my_slots = W.nslots / gridDim.x;
     for (uint32_t i = threadIdx.x; i < kWorkerOutCache; i += blockDim.x)
         ovalid[i] = 0u;
-    small_tables<false>(W.P, L);
+    small_tables<kRoute>(W.P, L);
 
     uint64_t t = __hip_atomic_load(W.next + blockIdx.x, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
@@ -2971,7 +2995,7 @@ __global__ __launch_bounds__(kSmallBlock) void yrss_burst_worker(WorkerParams W)
                            W.lens + (size_t)si * kWorkerMaxBurst, const_cast<uint8_t *>(P.win),
                            const_cast<uint16_t *>(P.len), W.fault + blockIdx.x, n, frames};
         if (n) {
-            small_burst_body<false, 1>(P, W.G, gio,
+            small_burst_body<kRoute, 1, kRoute>(P, W.G, gio,
                                     BurstIO{static_cast<uint32_t *>(out_ptr(2)),
                                             static_cast<uint32_t *>(out_ptr(3)),
                                             windows ? 0u : 1u,
@@ -3169,6 +3193,9 @@ struct yrss_ctx {
     struct WorkerState {
         bool on = false;           // yrss_worker_start called
         bool running = false;      // a worker launch may still be in flight
+        bool route = false;        // yrss_worker_start_route: the lists are the routed ones
+        uint16_t route_lq = 0;     // route: the lcore's own queue
+        uint32_t nbk = 0;          // buckets of the lists: nb, or nb + 2 route classes
         uint32_t nslots = 0, nblocks = 0, qs_stride = 0;
         uint64_t idle_ticks = 0, life_ticks = 0;
         uint32_t poll_sleep = 1;
@@ -3529,7 +3556,7 @@ int ensure_burst(yrss_ctx *c, uint32_t n)
         return 0;
     free_burst(c);
     const uint32_t cap = std::max<uint32_t>(n, 1024u);
-    const size_t nbk = (size_t)c->nb + 1;
+    const size_t nbk = (size_t)c->nb + 3;   // (the routed lists: nb_queues + 4 offsets)
     YRSS_HIP(hipHostMalloc((void **)&c->h_win, (size_t)cap * YRSS_WIN_FULL, hipHostMallocDefault));
     YRSS_HIP(hipHostMalloc((void **)&c->h_len, (size_t)cap * 2, hipHostMallocDefault));
     YRSS_HIP(hipHostMalloc((void **)&c->h_q, (size_t)cap * 2, hipHostMallocDefault));
@@ -3716,8 +3743,10 @@ bool small_ok(const yrss_ctx *c, uint32_t n)
 // host_burst: a host-resident burst on the context stream, completed by the
 // host spinning on the kernel's completion word; otherwise a device batch on
 // the caller's stream (no completion word).
+// route: the route instantiation over nq + 3 classes (S.P.route_lq set by the
+// caller; the KNI rule is the context's), S.qidx / S.qstart the routed lists.
 int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = true,
-                 hipStream_t stream = nullptr)
+                 hipStream_t stream = nullptr, bool route = false)
 {
     const ParseParams &proto = c->proto;
     ParseParams &P = S.P;
@@ -3740,9 +3769,15 @@ int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = tru
     } else {
         S.done = nullptr;
     }
-    const size_t lds = small_lds(c->nb, filter);
+    if (route) {
+        P.nb = proto.nb + 2u;
+        P.route_accept = c->kni_accept ? 1 : 0;
+    }
+    const size_t lds = small_lds(P.nb, filter || route);
     const dim3 grid(1);
-    if (filter)
+    if (route)
+        hipLaunchKernelGGL((yrss_burst_small<true, true>), grid, dim3(kSmallBlock), lds, stream, S);
+    else if (filter)
         hipLaunchKernelGGL(yrss_burst_small<true>, grid, dim3(kSmallBlock), lds, stream, S);
     else
         hipLaunchKernelGGL(yrss_burst_small<false>, grid, dim3(kSmallBlock), lds, stream, S);
@@ -3795,9 +3830,14 @@ int finish_burst(yrss_ctx *c)
 // c->h_len at stride W; results go to the caller's host arrays (NULL = not
 // wanted) when the burst completes (finish_burst).  want_hash computes the
 // hash into the staging even without out_hash (hash.rss write-back).
+// route_lq >= 0 (yrss_route_lists_*; the caller checked n and nb_queues): the
+// lists are the routed ones for the lcore whose queue is route_lq, always in
+// one launch.
 int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_t *out_hash,
-                    uint32_t *out_qidx, uint32_t *out_qstart, int8_t *out_filter, bool want_hash)
+                    uint32_t *out_qidx, uint32_t *out_qstart, int8_t *out_filter, bool want_hash,
+                    int route_lq = -1)
 {
+    const bool route = route_lq >= 0;
     hipStream_t s = c->stream;
     const bool compact = out_qidx && out_qstart;
     want_hash = want_hash || out_hash;
@@ -3807,9 +3847,10 @@ int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_
     p.outs[0] = {out_q, c->h_q, (size_t)n * 2, false};
     p.outs[1] = {out_hash, c->h_hash, (size_t)n * 4, false};
     p.outs[2] = {compact ? out_qidx : nullptr, c->h_qidx, (size_t)n * 4, false};
-    p.outs[3] = {compact ? out_qstart : nullptr, c->h_qstart, (c->nb + 1) * 4, false};
+    p.outs[3] = {compact ? out_qstart : nullptr, c->h_qstart, (c->nb + (route ? 3 : 1)) * 4,
+                 false};
     p.outs[4] = {out_filter, c->h_filter, n, false};
-    if (small_ok(c, n)) {
+    if (route || small_ok(c, n)) {
         // the kernel reads the staged windows and writes the staging in place
         SmallParams S;
         memset(&S, 0, sizeof(S));
@@ -3822,7 +3863,8 @@ int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_
         S.P.filter = out_filter ? c->dh_filter : nullptr;
         S.qidx = compact ? c->dh_qidx : nullptr;
         S.qstart = compact ? c->dh_qstart : nullptr;
-        int rc = small_launch(c, S, out_filter != nullptr);
+        S.P.route_lq = route ? (uint16_t)route_lq : 0;
+        int rc = small_launch(c, S, out_filter != nullptr, true, nullptr, route);
         if (rc)
             return rc;
         p.active = true;
@@ -3910,6 +3952,44 @@ int gather_mbufs(yrss_ctx *c, void *const *mbufs, uint32_t n, uint32_t *W_out)
     }
     *W_out = W;
     return 0;
+}
+
+// The same for frames given as (data pointer, data_len) pairs.
+int gather_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len, uint32_t n,
+                  uint32_t *W_out)
+{
+    int rc = ensure_burst(c, n);
+    if (rc)
+        return rc;
+    uint32_t maxlen = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        maxlen = std::max<uint32_t>(maxlen, len[i]);
+    const uint32_t W = host_stride(maxlen);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (i + 16u < n)
+            __builtin_prefetch(data[i + 16u]);
+        const uint32_t L = len[i];
+        memcpy(c->h_win + (size_t)i * W, data[i], L < W ? L : W);
+        c->h_len[i] = (uint16_t)L;
+    }
+    *W_out = W;
+    return 0;
+}
+
+// yrss_route_lists_burst / _frames: what is refused before anything is
+// touched, and the empty burst.  1: done (n == 0), 0: go on, < 0: refused.
+int route_lists_begin(yrss_ctx *c, uint32_t n, const void *src, const void *src2,
+                      int16_t *out_q, uint32_t *out_ridx, uint32_t *out_rstart)
+{
+    if (!c || !out_rstart || (n && (!src || !src2 || !out_q || !out_ridx)))
+        return -EINVAL;
+    if (n > kSmallMaxPkts || c->cfg.nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
+        return -ENOTSUP;
+    if (n == 0) {
+        memset(out_rstart, 0, (c->nb + 3u) * sizeof(uint32_t));
+        return 1;
+    }
+    return begin_burst(c);
 }
 
 }  // namespace
@@ -4114,6 +4194,17 @@ int yrss_set_kni(yrss_ctx *c, int enable, const char *method, const char *tcp_po
             return -EINVAL;
     } else if (enable) {
         return -EINVAL;                      // ff_config.c:543-546
+    }
+    if (c->w.on && c->w.route) {
+        // a route worker carries the KNI state of its launch: a pending burst
+        // keeps it, otherwise the launch goes and the next submit starts one
+        // with the new state
+        if (c->w.pending)
+            return -EBUSY;
+        YRSS_HIP(hipSetDevice(c->device));
+        const int hrc = worker_halt(c);
+        if (hrc)
+            return hrc;
     }
     memset(c->kni_bm, 0, sizeof(c->kni_bm));
     kni_parse_ports(tcp_ports, c->kni_bm);
@@ -4524,21 +4615,28 @@ int yrss_dispatch_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t
     if (rc)
         return rc;
     YRSS_HIP(hipSetDevice(c->device));
-    if ((rc = ensure_burst(c, n)) != 0)
+    uint32_t W = 0;
+    if ((rc = gather_frames(c, data, len, n, &W)) != 0)
         return rc;
-    uint32_t maxlen = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        maxlen = std::max<uint32_t>(maxlen, len[i]);
-    const uint32_t W = host_stride(maxlen);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (i + 16u < n)
-            __builtin_prefetch(data[i + 16u]);
-        const uint32_t L = len[i];
-        memcpy(c->h_win + (size_t)i * W, data[i], L < W ? L : W);
-        c->h_len[i] = (uint16_t)L;
-    }
     if ((rc = classify_staged(c, n, W, out_q, out_hash, out_qidx, out_qstart, nullptr,
                               false)) != 0)
+        return rc;
+    return finish_burst(c);
+}
+
+int yrss_route_lists_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len,
+                            uint32_t n, uint16_t queue_id, int16_t *out_q, uint32_t *out_hash,
+                            int8_t *out_filter, uint32_t *out_ridx, uint32_t *out_rstart)
+{
+    int rc = route_lists_begin(c, n, data, len, out_q, out_ridx, out_rstart);
+    if (rc)
+        return rc < 0 ? rc : 0;
+    YRSS_HIP(hipSetDevice(c->device));
+    uint32_t W = 0;
+    if ((rc = gather_frames(c, data, len, n, &W)) != 0)
+        return rc;
+    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_ridx, out_rstart, out_filter, false,
+                              (int)queue_id)) != 0)
         return rc;
     return finish_burst(c);
 }
@@ -4650,6 +4748,28 @@ int yrss_dispatch_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, int16_t *ou
     if (wb)
         c->pend.wb_mbufs = mbufs;
     return end_burst(c, flags);
+}
+
+int yrss_route_lists_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, uint16_t queue_id,
+                           int16_t *out_q, uint32_t *out_hash, int8_t *out_filter,
+                           uint32_t *out_ridx, uint32_t *out_rstart, uint32_t flags)
+{
+    if (flags & ~YRSS_F_WRITE_RSS)
+        return -EINVAL;
+    int rc = route_lists_begin(c, n, mbufs, mbufs, out_q, out_ridx, out_rstart);
+    if (rc)
+        return rc < 0 ? rc : 0;
+    YRSS_HIP(hipSetDevice(c->device));
+    uint32_t W = 0;
+    if ((rc = gather_mbufs(c, mbufs, n, &W)) != 0)
+        return rc;
+    const bool wb = (flags & YRSS_F_WRITE_RSS) != 0;
+    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_ridx, out_rstart, out_filter, wb,
+                              (int)queue_id)) != 0)
+        return rc;
+    if (wb)
+        c->pend.wb_mbufs = mbufs;
+    return finish_burst(c);
 }
 
 int yrss_register_host_memory(yrss_ctx *c, void *base, size_t len)
@@ -5121,6 +5241,14 @@ int worker_launch(yrss_ctx *c)
     W.P.fault = nullptr;   // per burst: W.brec, then the slot's srec entry
     W.P.kni_bm = c->d_kni;
     W.P.kni_enable = 0;
+    if (w.route) {
+        // the KNI state as the context holds it now: yrss_set_kni halts a
+        // route worker, so a launch never outlives the state it was given
+        W.P.nb = w.nbk;
+        W.P.kni_enable = c->kni_enable ? 1u : 0u;
+        W.P.route_lq = w.route_lq;
+        W.P.route_accept = c->kni_accept ? 1 : 0;
+    }
     const yrss_mbuf_layout &ml = c->cfg.mbuf;
     W.G.nranges = c->nranges;
     W.G.off_buf_addr = ml.off_buf_addr;
@@ -5144,8 +5272,12 @@ int worker_launch(yrss_ctx *c)
     W.idle_ticks = w.idle_ticks;
     W.life_ticks = w.life_ticks;
     W.poll_sleep = w.poll_sleep;
-    hipLaunchKernelGGL(yrss_burst_worker, dim3(w.nblocks), dim3(kSmallBlock),
-                       worker_lds(c->nb), w.stream, W);
+    if (w.route)
+        hipLaunchKernelGGL(yrss_burst_worker<true>, dim3(w.nblocks), dim3(kSmallBlock),
+                           worker_lds(w.nbk, true), w.stream, W);
+    else
+        hipLaunchKernelGGL(yrss_burst_worker<false>, dim3(w.nblocks), dim3(kSmallBlock),
+                           worker_lds(c->nb), w.stream, W);
     YRSS_HIP(hipGetLastError());
     w.running = true;
     return 0;
@@ -5166,22 +5298,23 @@ int worker_ensure(yrss_ctx *c)
     return rc ? rc : worker_launch(c);
 }
 
-}  // namespace
-
-extern "C" {
-
-int yrss_worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks)
+int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uint16_t queue_id)
 {
     if (!c || nblocks < 1 || nblocks > YRSS_WORKER_MAX_BLOCKS || nslots < nblocks ||
         nslots > YRSS_WORKER_MAX_SLOTS || nslots % nblocks || c->nb > kSmallMaxNb)
         return -EINVAL;
+    if (route && c->cfg.nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
+        return -ENOTSUP;
     if (c->w.on)
         return -EBUSY;
     YRSS_HIP(hipSetDevice(c->device));
     auto &w = c->w;
+    w.route = route;
+    w.route_lq = queue_id;
+    w.nbk = route ? c->nb + 2u : c->nb;
     w.nslots = nslots;
     w.nblocks = nblocks;
-    w.qs_stride = (c->nb + 1u + 15u) & ~15u;
+    w.qs_stride = (w.nbk + 1u + 15u) & ~15u;
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess ||
         khz <= 0)
@@ -5248,6 +5381,20 @@ int yrss_worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks)
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+int yrss_worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks)
+{
+    return worker_start(c, nslots, nblocks, false, 0);
+}
+
+int yrss_worker_start_route(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, uint16_t queue_id)
+{
+    return worker_start(c, nslots, nblocks, true, queue_id);
+}
+
 }  // extern "C"
 
 namespace {
@@ -5277,7 +5424,7 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     const size_t base = (size_t)si * kWorkerMaxBurst;
     void *const user[4] = {out_q, out_hash, out_qidx, out_qstart};
     const size_t bytes[4] = {(size_t)n * 2u, (size_t)n * 4u, (size_t)n * 4u,
-                             (c->nb + 1u) * 4u};
+                             (w.nbk + 1u) * 4u};
     void *const stage[4] = {w.d_q + base, w.d_hash + base, w.d_qidx + base,
                             w.d_qstart + (size_t)si * w.qs_stride};
     uint8_t copy = 0;
@@ -5424,7 +5571,7 @@ int yrss_worker_poll(yrss_ctx *c, uint64_t ticket, int wait)
     if (o.copy & 4u)
         memcpy(o.qidx, w.qidx + base, (size_t)o.n * 4u);
     if (o.copy & 8u)
-        memcpy(o.qstart, w.qstart + (size_t)si * w.qs_stride, (c->nb + 1u) * 4u);
+        memcpy(o.qstart, w.qstart + (size_t)si * w.qs_stride, (w.nbk + 1u) * 4u);
     return 0;
 }
 

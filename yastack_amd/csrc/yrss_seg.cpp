@@ -14,9 +14,14 @@
 // route buckets a segment) and performs process_packets' hand-off
 // (ff_dpdk_if.c:1058-1140) with list walks alone: what yrss_route_burst decides
 // per packet from q and filter, the parse kernel has already decided.
+// yrss_route_lists does the same from the one global routed list of a host
+// burst or a route worker's burst (yrss_route_lists_*, yrss_worker_start_route);
+// both run the one hand-off routine, over 8-bit or 32-bit indices.
 #include <errno.h>
 #include <stdint.h>
 #include <string.h>
+
+#include <new>
 
 #include "yrss.h"
 
@@ -98,6 +103,95 @@ static int route_seg_valid(const uint8_t *seg_idx, const uint16_t *seg_off, uint
     return 0;
 }
 
+}  // extern "C"
+
+// process_packets' hand-off (ff_dpdk_if.c:1058-1140) over one set of finished
+// route lists: idx the packet indices (into m and, offset by first, into
+// filter) grouped by route class, o the nq + 4 offsets, already validated.
+// Shared by the segments of yrss_route_seg (8-bit indices, 16-bit offsets) and
+// the one global list of yrss_route_lists (32-bit both).  Scratch from the
+// caller: cl (ARP packets x nq clones), kc (one KNI clone per ARP packet),
+// burst (as many objects as one ring can be offered: packets + ARP packets).
+template <typename Idx, typename Off>
+static void route_hand_off(const Idx *idx, const Off *o, void *const *m, uint32_t first,
+                           uint32_t nq, uint16_t queue_id, int kni_clone, const int8_t *filter,
+                           const struct yrss_route_ops *ops, void **out_local, void **out_kni,
+                           struct yrss_route_result *res, void **cl, void **kc, void **burst)
+{
+    // ARP kept on this lcore is deep-cloned to every other queue, in packet
+    // order, queue order inside a packet, then once more for KNI
+    // (ff_dpdk_if.c:1099-1129)
+    const Idx *arp = idx + o[nq + 2u];
+    const uint32_t na = (uint32_t)(o[nq + 3u] - o[nq + 2u]);
+    for (uint32_t a = 0; a < na; ++a) {
+        for (uint16_t j = 0; j < nq; ++j)
+            cl[(size_t)a * nq + j] = j != queue_id ? ops->clone(ops->user, m[arp[a]], j) : nullptr;
+        kc[a] = kni_clone ? ops->clone(ops->user, m[arp[a]], 0xFFFFu) : nullptr;
+    }
+    // one FIFO burst per ring: bucket j merged by packet index with the
+    // clones for j (a failed clone enqueues nothing, :1114-1118)
+    for (uint16_t j = 0; j < nq; ++j) {
+        if (j == queue_id)
+            continue;
+        uint32_t k = o[j], nb = 0, a = 0;
+        const uint32_t e = o[j + 1];
+        while (k < e || a < na) {
+            if (a < na && (k >= e || arp[a] < idx[k])) {
+                if (cl[(size_t)a * nq + j])
+                    burst[nb++] = cl[(size_t)a * nq + j];
+                ++a;
+            } else {
+                burst[nb++] = m[idx[k++]];
+            }
+        }
+        unsigned done = nb ? ops->enqueue(ops->user, j, burst, nb) : 0u;
+        if (done > nb)
+            done = nb;
+        res->n_ring[j] += done;
+        for (uint32_t r = done; r < nb; ++r) {      // ring full: free (:1090)
+            ops->release(ops->user, burst[r]);
+            res->n_freed++;
+        }
+    }
+    // ret < 0 || ret >= nb_queues: freed (:1080-1083)
+    for (uint32_t k = o[nq]; k < o[nq + 1u]; ++k) {
+        ops->release(ops->user, m[idx[k]]);
+        res->n_freed++;
+    }
+    if (queue_id >= nq)
+        return;
+    // local input, in packet order: the local bucket and the ARP packets
+    uint32_t k = o[queue_id], a = 0;
+    const uint32_t e = o[queue_id + 1u];
+    while (k < e || a < na) {
+        if (a < na && (k >= e || arp[a] < idx[k])) {
+            out_local[res->n_local++] = m[arp[a++]];
+            res->n_arp++;
+        } else {
+            const uint32_t i = idx[k++];
+            if (filter && (filter[first + i] == YRSS_FILTER_TRUNC ||
+                           filter[first + i] == YRSS_FILTER_LOOP))
+                res->n_unresolved++;
+            out_local[res->n_local++] = m[i];
+        }
+    }
+    // ff_kni_enqueue, in packet order: the KNI bucket and the KNI clones
+    k = o[nq + 1u];
+    a = 0;
+    const uint32_t ek = o[nq + 2u];
+    while (k < ek || a < na) {
+        if (a < na && (k >= ek || arp[a] < idx[k])) {
+            if (kc[a])
+                out_kni[res->n_kni++] = kc[a];
+            ++a;
+        } else {
+            out_kni[res->n_kni++] = m[idx[k++]];
+        }
+    }
+}
+
+extern "C" {
+
 int yrss_route_seg(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
                    uint16_t nb_queues, uint16_t queue_id, int kni_clone, const int8_t *filter,
                    void *const *objs, const struct yrss_route_ops *ops, void **out_local,
@@ -115,84 +209,62 @@ int yrss_route_seg(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
     if (route_seg_valid(seg_idx, seg_off, n, nq, local_ok))
         return -EINVAL;
     const uint32_t nseg = n / YRSS_SEG_PKTS + (n % YRSS_SEG_PKTS ? 1u : 0u);
-    for (uint32_t s = 0; s < nseg; ++s) {
-        const uint16_t *o = seg_off + (size_t)s * (nrb + 1u);
-        const uint8_t *idx = seg_idx + (size_t)s * YRSS_SEG_PKTS;
-        void *const *m = objs + (size_t)s * YRSS_SEG_PKTS;
-        // ARP kept on this lcore is deep-cloned to every other queue, in packet
-        // order, queue order inside a packet, then once more for KNI
-        // (ff_dpdk_if.c:1099-1129)
-        const uint8_t *arp = idx + o[nq + 2u];
-        const uint32_t na = (uint32_t)(o[nq + 3u] - o[nq + 2u]);
-        void *cl[YRSS_SEG_PKTS][YRSS_ROUTE_SEG_MAX_QUEUES];
-        void *kc[YRSS_SEG_PKTS];
-        for (uint32_t a = 0; a < na; ++a) {
-            for (uint16_t j = 0; j < nq; ++j)
-                cl[a][j] = j != queue_id ? ops->clone(ops->user, m[arp[a]], j) : nullptr;
-            kc[a] = kni_clone ? ops->clone(ops->user, m[arp[a]], 0xFFFFu) : nullptr;
-        }
-        // one FIFO burst per ring: bucket j merged by packet index with the
-        // clones for j (a failed clone enqueues nothing, :1114-1118)
-        void *burst[YRSS_SEG_PKTS];
-        for (uint16_t j = 0; j < nq; ++j) {
-            if (j == queue_id)
-                continue;
-            uint32_t k = o[j], nb = 0, a = 0;
-            const uint32_t e = o[j + 1];
-            while (k < e || a < na) {
-                if (a < na && (k >= e || arp[a] < idx[k])) {
-                    if (cl[a][j])
-                        burst[nb++] = cl[a][j];
-                    ++a;
-                } else {
-                    burst[nb++] = m[idx[k++]];
-                }
-            }
-            unsigned done = nb ? ops->enqueue(ops->user, j, burst, nb) : 0u;
-            if (done > nb)
-                done = nb;
-            res->n_ring[j] += done;
-            for (uint32_t r = done; r < nb; ++r) {      // ring full: free (:1090)
-                ops->release(ops->user, burst[r]);
-                res->n_freed++;
-            }
-        }
-        // ret < 0 || ret >= nb_queues: freed (:1080-1083)
-        for (uint32_t k = o[nq]; k < o[nq + 1u]; ++k) {
-            ops->release(ops->user, m[idx[k]]);
-            res->n_freed++;
-        }
-        if (!local_ok)
-            continue;
-        // local input, in packet order: the local bucket and the ARP packets
-        uint32_t k = o[queue_id], a = 0;
-        const uint32_t e = o[queue_id + 1u];
-        while (k < e || a < na) {
-            if (a < na && (k >= e || arp[a] < idx[k])) {
-                out_local[res->n_local++] = m[arp[a++]];
-                res->n_arp++;
-            } else {
-                const uint32_t i = s * YRSS_SEG_PKTS + idx[k++];
-                if (filter && (filter[i] == YRSS_FILTER_TRUNC || filter[i] == YRSS_FILTER_LOOP))
-                    res->n_unresolved++;
-                out_local[res->n_local++] = objs[i];
-            }
-        }
-        // ff_kni_enqueue, in packet order: the KNI bucket and the KNI clones
-        k = o[nq + 1u];
-        a = 0;
-        const uint32_t ek = o[nq + 2u];
-        while (k < ek || a < na) {
-            if (a < na && (k >= ek || arp[a] < idx[k])) {
-                if (kc[a])
-                    out_kni[res->n_kni++] = kc[a];
-                ++a;
-            } else {
-                out_kni[res->n_kni++] = m[idx[k++]];
-            }
-        }
-    }
+    void *cl[YRSS_SEG_PKTS * YRSS_ROUTE_SEG_MAX_QUEUES];
+    void *kc[YRSS_SEG_PKTS];
+    void *burst[YRSS_SEG_PKTS];
+    for (uint32_t s = 0; s < nseg; ++s)
+        route_hand_off(seg_idx + (size_t)s * YRSS_SEG_PKTS, seg_off + (size_t)s * (nrb + 1u),
+                       objs + (size_t)s * YRSS_SEG_PKTS, s * YRSS_SEG_PKTS, nq, queue_id,
+                       kni_clone, filter, ops, out_local, out_kni, res, cl, kc, burst);
     return 0;
+}
+
+int yrss_route_lists(const uint32_t *ridx, const uint32_t *rstart, uint32_t n,
+                     uint16_t nb_queues, uint16_t queue_id, int kni_primary,
+                     const int8_t *filter, void *const *objs, const struct yrss_route_ops *ops,
+                     void **out_local, void **out_kni, struct yrss_route_result *res)
+{
+    if (!ops || !ops->enqueue || !ops->clone || !ops->release || !res || !rstart)
+        return -EINVAL;
+    if (nb_queues < 1 || nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
+        return -EINVAL;
+    if (n && (!ridx || !objs || !out_local || !out_kni))
+        return -EINVAL;
+    const uint32_t nq = nb_queues, nrb = nq + 3u;
+    memset(res, 0, sizeof(*res));
+    // the offsets 0 .. n and monotone; no local queue: nothing can be KNI or
+    // local ARP
+    if (rstart[0] != 0 || rstart[nrb] != n)
+        return -EINVAL;
+    for (uint32_t b = 0; b < nrb; ++b)
+        if (rstart[b + 1] < rstart[b])
+            return -EINVAL;
+    if (queue_id >= nq && rstart[nq + 1u] != n)
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    // scratch: the ARP packets' clones, one ring's burst (at most every
+    // packet once, itself or as its clone), and the seen bits of the check
+    // that every index is below n and present once (a packet handed off twice
+    // would be freed twice)
+    const size_t na = rstart[nq + 3u] - rstart[nq + 2u];
+    const size_t words = ((size_t)n + 63u) / 64u;
+    void **scratch = new (std::nothrow) void *[na * nq + na + n];
+    uint64_t *seen = new (std::nothrow) uint64_t[words]();
+    int rc = scratch && seen ? 0 : -ENOMEM;
+    for (uint32_t k = 0; rc == 0 && k < n; ++k) {
+        const uint32_t i = ridx[k];
+        if (i >= n || (seen[i >> 6] >> (i & 63u)) & 1u)
+            rc = -EINVAL;
+        else
+            seen[i >> 6] |= 1ull << (i & 63u);
+    }
+    if (rc == 0)
+        route_hand_off(ridx, rstart, objs, 0u, nq, queue_id, kni_primary, filter, ops, out_local,
+                       out_kni, res, scratch, scratch + na * nq, scratch + na * nq + na);
+    delete[] scratch;
+    delete[] seen;
+    return rc;
 }
 
 }  // extern "C"

@@ -368,10 +368,23 @@ class SoftRss:
         self._ck(rc, "yrss_wait")
 
     # -- persistent burst worker ------------------------------------------------
-    def worker_start(self, nslots: int = 16, nblocks: int = 4) -> None:
-        """Start the persistent small-burst worker (``yrss_worker_start``)."""
-        abi.check(self._lib.yrss_worker_start(self._ctx, nslots, nblocks), "yrss_worker_start")
+    def worker_start(self, nslots: int = 16, nblocks: int = 4,
+                     route_queue_id: int | None = None) -> None:
+        """Start the persistent small-burst worker (``yrss_worker_start``).
+        With ``route_queue_id`` (``yrss_worker_start_route``, nb_queues <= 61)
+        every burst's ``qidx`` / ``qstart`` are the routed lists for the lcore
+        whose queue that is: packet indices grouped by route class
+        (``segments.route_buckets``) and nb_queues + 4 offsets, under the KNI
+        state of the last :meth:`set_kni`; :meth:`route_lists` hands them off."""
+        if route_queue_id is None:
+            abi.check(self._lib.yrss_worker_start(self._ctx, nslots, nblocks),
+                      "yrss_worker_start")
+        else:
+            abi.check(self._lib.yrss_worker_start_route(self._ctx, nslots, nblocks,
+                                                        route_queue_id),
+                      "yrss_worker_start_route")
         self._wk = {}
+        self._wk_offsets = self.nb_queues + (2 if route_queue_id is None else 4)
 
     def worker_submit(self, mbuf_ptrs: np.ndarray, want_hash=True, compact=True,
                       write_rss=False) -> int:
@@ -382,7 +395,7 @@ class SoftRss:
         q = np.empty(max(n, 1), np.int16)
         h = np.empty(max(n, 1), np.uint32) if want_hash else None
         qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self.nb_queues + 2, np.uint32) if compact else None
+        qs = np.empty(self._wk_offsets, np.uint32) if compact else None
         t = ctypes.c_uint64()
         rc = self._lib.yrss_worker_submit(self._ctx, _ptr(mb), n, _ptr(q), _ptr(h), _ptr(qi),
                                           _ptr(qs), abi.F_WRITE_RSS if write_rss else 0,
@@ -404,7 +417,7 @@ class SoftRss:
         q = np.empty(max(n, 1), np.int16)
         h = np.empty(max(n, 1), np.uint32) if want_hash else None
         qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self.nb_queues + 2, np.uint32) if compact else None
+        qs = np.empty(self._wk_offsets, np.uint32) if compact else None
         t = ctypes.c_uint64()
         rc = self._lib.yrss_worker_submit_frames(self._ctx, _ptr(dp), _ptr(ln), n, _ptr(q),
                                                  _ptr(h), _ptr(qi), _ptr(qs), ctypes.byref(t))
@@ -422,7 +435,7 @@ class SoftRss:
         q = np.empty(max(n, 1), np.int16)
         h = np.empty(max(n, 1), np.uint32) if want_hash else None
         qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self.nb_queues + 2, np.uint32) if compact else None
+        qs = np.empty(self._wk_offsets, np.uint32) if compact else None
         t = ctypes.c_uint64()
         rc = self._lib.yrss_worker_submit_windows(self._ctx, _ptr(win), stride, _ptr(ln), n,
                                                   _ptr(q), _ptr(h), _ptr(qi), _ptr(qs),
@@ -507,6 +520,93 @@ class SoftRss:
                                         ctypes.byref(ops), _ptr(local), _ptr(kni),
                                         ctypes.byref(res))
         abi.check(rc, "yrss_route_burst")
+        return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
+
+    def _route_lists_out(self, n, want_hash, want_filter):
+        return (np.empty(max(n, 1), np.int16),
+                np.empty(max(n, 1), np.uint32) if want_hash else None,
+                np.empty(max(n, 1), np.int8) if want_filter else None,
+                np.empty(max(n, 1), np.uint32), np.empty(self.nb_queues + 4, np.uint32))
+
+    def route_lists_frames(self, frames, queue_id: int, want_hash=True,
+                           want_filter=True) -> DispatchResult:
+        """Classify a list of frames (bytes) into process_packets' hand-off
+        classes for the lcore whose queue is ``queue_id``, in one launch
+        (``yrss_route_lists_frames``: n <= 4096, nb_queues <= 61).  The
+        result's ``qidx`` / ``qstart`` are the routed lists: packet indices
+        grouped by route class and nb_queues + 4 offsets."""
+        n = len(frames)
+        bufs = [np.frombuffer(bytes(f), dtype=np.uint8) if len(f) else np.zeros(1, np.uint8)
+                for f in frames]
+        ptrs = np.array([b.ctypes.data for b in bufs], dtype=np.uint64)
+        lens = np.array([len(f) for f in frames], dtype=np.uint16)
+        if np.any(lens != np.array([len(f) for f in frames])):
+            raise ValueError("frame longer than 65535 bytes")
+        q, h, f, ri, rs = self._route_lists_out(n, want_hash, want_filter)
+        rc = self._lib.yrss_route_lists_frames(self._ctx, _ptr(ptrs), _ptr(lens), n, queue_id,
+                                               _ptr(q), _ptr(h), _ptr(f), _ptr(ri), _ptr(rs))
+        self._ck(rc, "yrss_route_lists_frames")
+        return DispatchResult(q[:n], None if h is None else h[:n], ri[:n], rs,
+                              None if f is None else f[:n])
+
+    def route_lists_burst(self, mbuf_ptrs: np.ndarray, queue_id: int, want_hash=True,
+                          want_filter=True, write_rss=False) -> DispatchResult:
+        """The same for a burst of ``struct rte_mbuf *`` (uint64 addresses;
+        ``yrss_route_lists_burst``)."""
+        mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
+        n = int(mb.size)
+        q, h, f, ri, rs = self._route_lists_out(n, want_hash, want_filter)
+        rc = self._lib.yrss_route_lists_burst(self._ctx, _ptr(mb), n, queue_id, _ptr(q), _ptr(h),
+                                              _ptr(f), _ptr(ri), _ptr(rs),
+                                              abi.F_WRITE_RSS if write_rss else 0)
+        self._ck(rc, "yrss_route_lists_burst")
+        return DispatchResult(q[:n], None if h is None else h[:n], ri[:n], rs,
+                              None if f is None else f[:n])
+
+    def route_lists(self, result_or_arrays, objs, queue_id: int, enqueue, clone, release,
+                    kni_primary: bool = True):
+        """process_packets' hand-off from routed global lists
+        (``yrss_route_lists``), mirroring :meth:`route_seg`:
+        ``result_or_arrays`` is the DispatchResult of :meth:`route_lists_frames`
+        / :meth:`route_lists_burst` / a route worker's poll, or host arrays
+        ``(ridx, rstart)`` / ``(ridx, rstart, filter)``; ``objs`` the mbuf
+        addresses, ``queue_id`` the one the lists were built for.  Returns
+        (local list, kni list, RouteResult)."""
+        if isinstance(result_or_arrays, DispatchResult):
+            ridx, rstart, filt = (result_or_arrays.qidx, result_or_arrays.qstart,
+                                  result_or_arrays.filter)
+        else:
+            ridx, rstart, *rest = result_or_arrays
+            filt = rest[0] if rest else None
+        ridx = np.ascontiguousarray(np.asarray(ridx).reshape(-1)).view(np.uint32)
+        rstart = np.ascontiguousarray(np.asarray(rstart).reshape(-1)).view(np.uint32)
+        mb = np.ascontiguousarray(objs, dtype=np.uint64)
+        n = int(mb.size)
+        if filt is not None:
+            filt = np.ascontiguousarray(np.asarray(filt).reshape(-1)).view(np.int8)
+        # the C call sees raw pointers only: the sizes are checked here
+        if ridx.size < n or rstart.size < self.nb_queues + 4 or \
+                (filt is not None and filt.size < n):
+            raise ValueError("arrays shorter than the burst")
+
+        def _enq(user, queue, ptrs, cnt):
+            return int(enqueue(int(queue), [int(ptrs[i] or 0) for i in range(cnt)]))
+
+        def _clone(user, m, queue):
+            return int(clone(int(m or 0), int(queue)) or 0)
+
+        def _rel(user, m):
+            release(int(m or 0))
+
+        ops = abi.RouteOps(abi.ENQUEUE_FN(_enq), abi.CLONE_FN(_clone), abi.RELEASE_FN(_rel), None)
+        local = np.zeros(max(n, 1), np.uint64)
+        kni = np.zeros(max(n, 1), np.uint64)
+        res = abi.RouteResult()
+        rc = self._lib.yrss_route_lists(_ptr(ridx), _ptr(rstart), n, self.nb_queues, queue_id,
+                                        1 if self._kni_enable and kni_primary else 0, _ptr(filt),
+                                        _ptr(mb), ctypes.byref(ops), _ptr(local), _ptr(kni),
+                                        ctypes.byref(res))
+        abi.check(rc, "yrss_route_lists")
         return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
 
     def route_seg(self, result_or_arrays, objs, queue_id: int, enqueue, clone, release,

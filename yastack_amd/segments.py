@@ -17,7 +17,9 @@ twin of the C helper ``yrss_seg_to_lists``; :func:`to_lists_c` calls that helper
 The routed form of ``yrss_route_dev_seg`` is the same layout over nrb =
 nb_queues + 3 route buckets (:func:`route_buckets`: what process_packets,
 :1058-1140, does with the packet on the lcore whose queue is ``queue_id``);
-:func:`route_from` builds it from per-packet q and filter-class arrays.
+:func:`route_from` builds it from per-packet q and filter-class arrays;
+:func:`route_lists_from` gives the same classes as one global list (32-bit
+packet indices, one offset row), the form of the one-workgroup bursts.
 """
 from __future__ import annotations
 
@@ -88,6 +90,19 @@ def route_from(q: np.ndarray, fclass: np.ndarray, nb_queues: int, queue_id: int,
     segmented lists of per-packet q and filter-class arrays."""
     return from_buckets(route_buckets(q, fclass, nb_queues, queue_id, kni_enable, kni_accept),
                         nb_queues + 3)
+
+
+def route_lists_from(q: np.ndarray, fclass: np.ndarray, nb_queues: int, queue_id: int,
+                     kni_enable: bool, kni_accept: bool):
+    """(ridx uint32[n], rstart uint32[nb_queues + 4]): the routed global lists
+    of a one-workgroup burst (``yrss_route_lists_burst`` / ``_frames``, the
+    route worker), a stable sort by :func:`route_buckets`."""
+    bkt = route_buckets(q, fclass, nb_queues, queue_id, kni_enable, kni_accept).reshape(-1)
+    nrb = int(nb_queues) + 3
+    ridx = np.argsort(bkt, kind="stable").astype(np.uint32)
+    rstart = np.zeros(nrb + 1, np.uint32)
+    rstart[1:] = np.cumsum(np.bincount(bkt, minlength=nrb))
+    return ridx, rstart
 
 
 def to_lists(seg_idx: np.ndarray, seg_off: np.ndarray, n: int, nbk: int):

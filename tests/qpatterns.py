@@ -14,6 +14,12 @@ packet, fs/lib/ff_dpdk_if.c:1080-1083); `build` fancy-indexes them by an integer
 bucket sequence into (win, lens); the generators below make the sequences.
 Pure numpy, no GPU.  Whether a sequence was realised is checked by the caller
 (tests/test_qpatterns.py: exactly, for every configuration the GPU tests use).
+
+`route_exemplars` does the same over the nb_queues + 3 route classes of the
+routed lists (segments.route_buckets: the foreign rings, local, freed, KNI,
+local ARP), from the oracle's q and filter class; `family` then adds members
+whose subject is those classes (tests/test_qpatterns_route.py proves them,
+tests/test_gpu_qpatterns_route.py runs them).
 """
 from __future__ import annotations
 
@@ -33,13 +39,31 @@ class Exemplars:
     lens: np.ndarray       # [m] uint16
     q: np.ndarray          # [m] the oracle's q of every pool packet
     hash: np.ndarray       # [m] its hash
-    table: np.ndarray      # [nb_queues + 1, PER_BUCKET] pool indices, -1 = bucket unreachable
+    table: np.ndarray      # [nb, PER_BUCKET] pool indices, -1 = bucket unreachable
     nb_queues: int
     stride: int
+    # route_exemplars only: the buckets are the nb_queues + 3 route classes of
+    # segments.route_buckets for the lcore whose queue is queue_id
+    fclass: np.ndarray | None = None      # [m] the oracle's filter class
+    queue_id: int = -1
+
+    @property
+    def route(self) -> bool:
+        return self.fclass is not None
 
     @property
     def nb(self) -> int:
-        return self.nb_queues + 1
+        return self.nb_queues + (3 if self.route else 1)
+
+    def own(self) -> list:
+        """Reachable route classes the lcore keeps or frees itself: local,
+        freed, KNI, local ARP (every class but the foreign rings)."""
+        nq = self.nb_queues
+        return [b for b in self.reachable if b == self.queue_id or b >= nq]
+
+    def foreign(self) -> list:
+        """Reachable rings of the other queues."""
+        return [b for b in self.queues() if b != self.queue_id]
 
     @property
     def reachable(self) -> list:
@@ -67,9 +91,6 @@ def exemplars(oracle_mod, cfg, stride: int = 64, n_tcp: int | None = None) -> Ex
     The drop bucket's exemplars hold one packet of each kind that reaches it
     (q >= nb_queues, truncated) before further flows."""
     npr, nq, _soft, _only = cfg
-    if n_tcp is None:
-        n_tcp = 65536 if npr > 1024 else 8192
-    w, l = oracle_mod.synth(SYN_TCP4, n_tcp, first=12345, stride=stride)
     extra = [(ethertype_frame(0x0806), 64),
              (ipv4_frame("10.1.2.3", 5353, "10.3.2.1", 53, proto=17, length=64), 64)]
     if stride < 66:
@@ -77,9 +98,7 @@ def exemplars(oracle_mod, cfg, stride: int = 64, n_tcp: int | None = None) -> Ex
         # reference, not decidable from a 64-byte window
         extra.append((ipv4_frame("10.9.8.7", 4321, "10.7.8.9", 443, ihl=12, length=100,
                                  total_len=None), 100))
-    ew = np.stack([np.frombuffer(f[:stride], np.uint8) for f, _ in extra])
-    win = np.concatenate([w.reshape(n_tcp, stride), ew])
-    lens = np.concatenate([l, np.array([x for _, x in extra], np.uint16)])
+    win, lens, n_tcp = _pool(oracle_mod, npr, stride, n_tcp, extra)
     q, h = oracle_mod.dispatch_windows(win.reshape(-1), stride, lens, oracle_mod.cfg(*cfg))
     bkt = bucket_of(q, nq)
     table = np.full((nq + 1, PER_BUCKET), -1, np.int64)
@@ -100,6 +119,66 @@ def exemplars(oracle_mod, cfg, stride: int = 64, n_tcp: int | None = None) -> Ex
         if k:
             table[b] = np.resize(mine[:k], PER_BUCKET)    # cycle when fewer
     return Exemplars(win, lens, q, h, table, nq, stride)
+
+
+def _pool(oracle_mod, npr: int, stride: int, n_tcp: int | None, extra):
+    """(win [m, stride], lens [m], n_tcp): hashed TCP4 flows, then `extra`
+    (frame, data_len) pairs cut to the stride."""
+    if n_tcp is None:
+        n_tcp = 65536 if npr > 1024 else 8192
+    w, l = oracle_mod.synth(SYN_TCP4, n_tcp, first=12345, stride=stride)
+    ew = np.stack([np.frombuffer(f[:stride], np.uint8) for f, _ in extra])
+    win = np.concatenate([w.reshape(n_tcp, stride), ew])
+    lens = np.concatenate([l, np.array([x for _, x in extra], np.uint16)])
+    return win, lens, n_tcp
+
+
+UDP_DPORTS = (53, 9999, 25000, 40000)     # some on, some off any sensible udp_port list
+
+
+def route_exemplars(oracle_mod, cfg, queue_id: int, kni, tcp_ports, udp_ports,
+                    stride: int = 64, n_tcp: int | None = None) -> Exemplars:
+    """The same over the nb_queues + 3 route classes of segments.route_buckets
+    (b < nq, b != queue_id: ring of queue b; queue_id: local; nq: freed; nq + 1:
+    KNI; nq + 2: local ARP) for kni = (enable, "accept" | "reject") and the two
+    KNI port lists.  The pool is that of `exemplars` (the TCP flows carry
+    destination ports on both sides of a list such as "0-30000") plus what the
+    added classes need: UDP frames (q = 2) with several destination ports, a
+    RARP frame (q = 0, filter class UNKNOWN: with dispatch_only_core = 1 the
+    only packet on queue 0 that is not ARP) and, at stride 64, the truncated TCP
+    frame.  Classes come from the oracle's q (dispatch_windows) and filter class
+    (filter_windows) through the class rule; a class's exemplars hold the
+    frames that are no TCP flows first."""
+    from yastack_amd import segments
+    npr, nq, _soft, _only = cfg
+    enable, method = kni
+    extra = [(ethertype_frame(0x0806), 64), (ethertype_frame(0x8035), 64)]
+    extra += [(ipv4_frame("10.1.2.3", 5353, "10.3.2.1", dp, proto=17, length=64), 64)
+              for dp in UDP_DPORTS]
+    if stride < 66:
+        extra.append((ipv4_frame("10.9.8.7", 4321, "10.7.8.9", 443, ihl=12, length=100,
+                                 total_len=None), 100))
+    win, lens, n_tcp = _pool(oracle_mod, npr, stride, n_tcp, extra)
+    q, h = oracle_mod.dispatch_windows(win.reshape(-1), stride, lens, oracle_mod.cfg(*cfg))
+    f = oracle_mod.filter_windows(win.reshape(-1), stride, lens, enable,
+                                  oracle_mod.kni_bitmap(tcp_ports), oracle_mod.kni_bitmap(udp_ports))
+    bkt = segments.route_buckets(q, f, nq, queue_id, enable, method == "accept")
+    nb = nq + 3
+    table = np.full((nb, PER_BUCKET), -1, np.int64)
+    for b in range(nb):
+        mine = np.nonzero(bkt == b)[0]
+        # one packet a flow and filter class: distinct (q, hash, class)
+        key = ((h[mine].astype(np.int64) << 24) | ((q[mine].astype(np.int64) & 0xFFFF) << 8) |
+               (f[mine].astype(np.int64) & 0xFF))
+        mine = mine[np.sort(np.unique(key, return_index=True)[1])]
+        special = mine[mine >= n_tcp]
+        over = mine[(mine < n_tcp) & (q[mine] >= nq)][:1]
+        rest = np.setdiff1d(mine, np.concatenate([special, over]), assume_unique=True)
+        mine = np.concatenate([special[:PER_BUCKET - 1], over, rest])
+        k = min(mine.size, PER_BUCKET)
+        if k:
+            table[b] = np.resize(mine[:k], PER_BUCKET)
+    return Exemplars(win, lens, q, h, table, nq, stride, fclass=f, queue_id=queue_id)
 
 
 def choose(pattern, ex: Exemplars) -> np.ndarray:
@@ -238,6 +317,8 @@ def family(name: str, n: int, ex: Exemplars, chunk: int, span: int) -> list:
     drop = nq if nq in reach else None
     mid = queues[len(queues) // 2]
     out = []
+    if ex.route and name in ("all_but_one", "runs", "zipf"):
+        return _route_family(name, n, ex, chunk, span)
     if name == "all_but_one":
         big = list(dict.fromkeys([queues[0], mid, queues[-1]] + ([drop] if drop is not None else [])))
         if len(reach) < 2:
@@ -261,6 +342,8 @@ def family(name: str, n: int, ex: Exemplars, chunk: int, span: int) -> list:
             if len(keep) == 1:       # one bucket only would be the one-list shortcut
                 keep = list(dict.fromkeys(keep + [reach[0], reach[-1]]))[:2]
             out.append((f"keep{k}", sparse(n, keep, seed=k + 1)))
+        if ex.route and len(ex.own()) >= 2:      # the foreign rings all stay empty
+            out.append(("keep-own", sparse(n, ex.own(), seed=4)))
     elif name == "late_and_early":
         # the carried bucket from the middle, the first-/last-span ones from the ends
         if len(reach) >= 4:
@@ -278,6 +361,72 @@ def family(name: str, n: int, ex: Exemplars, chunk: int, span: int) -> list:
             out.append((f"s{seed}", zipf(n, reach, seed)))
     else:
         raise ValueError(name)
+    return out
+
+
+ROUTE_RUNS = (1, 15, 16, 17, 63, 64, 65, 255, 256, 257)
+
+
+def _route_family(name: str, n: int, ex: Exemplars, chunk: int, span: int) -> list:
+    """all_but_one, runs and zipf over route classes: the classes the routing
+    adds (local, freed, KNI, local ARP: ex.own()) are the subject, and every
+    reachable class appears in some member of each family."""
+    reach, own, foreign = ex.reachable, ex.own(), ex.foreign()
+    out = []
+    if name == "all_but_one":
+        if len(reach) < 2:
+            raise ValueError("all_but_one needs two buckets")
+        pos = list(dict.fromkeys(p for p in (0, n - 1, (n // 2) // chunk * chunk,
+                                              max(n // span, 1) * span - 1) if 0 <= p < n))
+        rings = list(dict.fromkeys([foreign[0], foreign[len(foreign) // 2], foreign[-1]])) \
+            if foreign else []
+        used = set()
+        # the big class is local, KNI, local ARP, freed; the stray a foreign ring
+        # (with one queue: another of the lcore's own classes)
+        for k, B in enumerate(own):
+            strays = rings or [b for b in own if b != B]
+            for j, p in enumerate(pos):
+                o = strays[(k + j) % len(strays)]
+                out.append((f"B{B}-o{o}@{p}", all_but_one(n, B, o, p)))
+                used |= {B, o}
+        # the roles swapped
+        for k, o in enumerate(own):
+            for j in range(2 if rings else 0):
+                B, p = rings[(k + j) % len(rings)], pos[(k + 2 * j) % len(pos)]
+                out.append((f"B{B}-o{o}@{p}", all_but_one(n, B, o, p)))
+                used |= {B, o}
+        # every ring not met so far strays once into a batch of an own class
+        for k, o in enumerate(b for b in reach if b not in used):
+            B, p = (own or reach)[k % len(own or reach)], pos[k % len(pos)]
+            if B == o:
+                B = reach[0] if reach[0] != o else reach[1]
+            out.append((f"B{B}-o{o}@{p}", all_but_one(n, B, o, p)))
+    elif name == "runs":
+        rs = sorted(set(ROUTE_RUNS + (chunk - 1, chunk, chunk + 1, span - 1, span, span + 1)))
+        for R in rs:
+            if R < 1 or (R > n and R != rs[0]):
+                continue
+            if len(own) >= 2:
+                out.append((f"own-R{R}", runs(n, own, R)))
+            out.append((f"all-R{R}", runs(n, reach, R)))
+        if len(own) == 1:            # the whole batch in that class
+            out.append(("own-all", runs(n, own, n)))
+        # a batch shorter than the class list: the rest of the list, R = 1
+        for off in range(n, len(reach), n):
+            out.append((f"all-R1+{off}", runs(n, reach[off:] + reach[:off], 1)))
+    else:
+        for seed in (11, 12):
+            out.append((f"s{seed}", zipf(n, reach, seed)))
+        # one packet of every class planted in a heavy-tailed draw over the own
+        # classes (as many members as a short batch needs to hold them all)
+        per = max(min(n // 2, len(reach)), 1)
+        m = -(-len(reach) // per)
+        for k in range(m):
+            p = zipf(n, own or reach, 13 + k)
+            plant = np.asarray(reach[k::m], np.int64)
+            at = np.random.default_rng(13 + k).choice(n, plant.size, replace=False)
+            p[at] = plant
+            out.append((f"s{13 + k}-every", p))
     return out
 
 
@@ -342,3 +491,91 @@ def host_aim(nb: int, n: int):
 
 def tune_id(tune: dict) -> str:
     return "-".join(f"{k}{v}" for k, v in tune.items()) or "default"
+
+
+# ---- the cases of tests/test_gpu_qpatterns_route.py -------------------------------
+# A route case is (cfg, queue_id, kni mode of route_helpers.KNI_MODES, stride);
+# the KNI port lists are route_helpers.TCP_PORTS / UDP_PORTS.
+# tests/test_qpatterns_route.py realises every family for every entry on the
+# CPU and pins each case's reachable classes.
+
+ROUTE_SEG_KINDS = tuple(
+    [((13, 13, 1, 0), qid, kni, 64) for qid, kni in ((0, "accept"), (2, "reject"), (13, "off"))] +
+    [((6, 4, 1, 0), qid, kni, 64) for qid, kni in ((0, "accept"), (2, "reject"))] +
+    [((3, 3, 1, 1), qid, kni, 64) for qid, kni in ((0, "accept"), (2, "off"))] +
+    [((1, 1, 1, 0), 0, "reject", 64)] +
+    [((13, 13, 1, 0), 0, "reject", 80)]           # full windows: nothing truncates
+)
+ROUTE_SEG_SIZES = (256, 257, 4097, 20000)
+ROUTE_SEG_BLOCKS = (0, 1)
+
+# one-launch bursts: 6, 16, 17 (one more ballot bit in peer_mask) and 64 route
+# classes (all six ballot bits; class 63 is local ARP).  nb_procs > nb_queues
+# where the freed class is to be reachable: the host paths stage what the frames
+# hold, so nothing truncates
+ROUTE_BURST_KINDS = (
+    ((5, 3, 1, 1), 0, "accept", 80), ((5, 3, 1, 0), 2, "reject", 80),
+    ((13, 13, 1, 0), 0, "reject", 80), ((16, 13, 1, 0), 2, "accept", 80),
+    ((14, 14, 1, 0), 0, "accept", 80), ((17, 14, 1, 0), 2, "reject", 80),
+    ((64, 61, 1, 0), 0, "accept", 80), ((61, 61, 1, 0), 2, "reject", 80),
+    ((64, 61, 1, 0), 61, "off", 80), ((64, 61, 1, 0), 0, "reject", 80),
+)
+ROUTE_BURST_SIZES = (64, 1024, 4096)
+ROUTE_BURST_AIM = (64, 1024)
+
+ROUTE_WORKER_KINDS = (
+    ((5, 3, 1, 0), 0, "accept", 80), ((5, 3, 1, 1), 2, "reject", 80),
+    ((64, 61, 1, 0), 0, "reject", 80), ((64, 61, 1, 0), 2, "accept", 80),
+)
+
+
+def route_kind_id(kind) -> str:
+    cfg, queue_id, kni, stride = kind
+    return f"{'x'.join(map(str, cfg))}-q{queue_id}-{kni}-s{stride}"
+
+
+def route_aims():
+    """Every (kind, n, chunk, span) some routed GPU case builds patterns for."""
+    seen = {}
+    for kind in ROUTE_SEG_KINDS:
+        for n in ROUTE_SEG_SIZES:
+            seen[(kind, n) + SEG_AIM] = None
+    for kind in ROUTE_BURST_KINDS:
+        for n in ROUTE_BURST_SIZES:
+            seen[(kind, n) + ROUTE_BURST_AIM] = None
+    for kind in ROUTE_WORKER_KINDS:
+        for n in WORKER_SIZES:
+            seen[(kind, n) + ROUTE_BURST_AIM] = None
+    return list(seen)
+
+
+_ROUTE_EX = {}
+
+
+def route_ex_for(oracle_mod, kind) -> Exemplars:
+    """route_exemplars of a route case, computed once."""
+    import route_helpers as rh
+    if kind not in _ROUTE_EX:
+        cfg, queue_id, kni, stride = kind
+        _ROUTE_EX[kind] = route_exemplars(oracle_mod, cfg, queue_id, rh.KNI_MODES[kni],
+                                          rh.TCP_PORTS, rh.UDP_PORTS, stride)
+    return _ROUTE_EX[kind]
+
+
+def route_oracle(oracle_mod, kind, win, lens, stride=None):
+    """The oracle's (q, hash, filter class) of built windows under a route case."""
+    import route_helpers as rh
+    cfg, _queue_id, kni, kstride = kind
+    stride = stride or kstride
+    q, h = oracle_mod.dispatch_windows(win, stride, lens, oracle_mod.cfg(*cfg))
+    f = oracle_mod.filter_windows(win, stride, lens, rh.KNI_MODES[kni][0],
+                                  oracle_mod.kni_bitmap(rh.TCP_PORTS),
+                                  oracle_mod.kni_bitmap(rh.UDP_PORTS))
+    return q, h, f
+
+
+def route_members(ex: Exemplars, n: int, chunk: int, span: int):
+    """Every member of every family as (name, class sequence)."""
+    for fam in FAMILIES:
+        for label, pat in family(fam, n, ex, chunk, span):
+            yield f"{fam}/{label}", pat

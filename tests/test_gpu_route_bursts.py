@@ -348,8 +348,9 @@ def _registered_windows():
     return a
 
 
-def _submit(eng, form, lo, n, o, wreg=None, stride=80, write_rss=False):
-    _, lens, _, ptrs, data = pool()
+def _submit(eng, form, lo, n, o, wreg=None, stride=80, write_rss=False, src=None):
+    """src: (lens, mbuf ptrs, frame data ptrs) to slice in place of pool()'s."""
+    lens, ptrs, data = src if src is not None else (pool()[1], pool()[3], pool()[4])
     t = ctypes.c_uint64()
     lib, ctx = eng._lib, eng._ctx
     if form == "mbufs":

@@ -365,8 +365,9 @@ int yrss_route_lists_frames(yrss_ctx *ctx, const uint8_t *const *data, const uin
 
 /* Host-only: process_packets' hand-off from routed global lists; the twin of
  * yrss_route_seg for one burst, with its arguments, callbacks and results
- * (kni_primary is its kni_clone: pass "KNI on && kni_primary").  What
- * yrss_route_burst does per packet from q and filter, done by list walks:
+ * (kni_primary is its kni_clone: pass "KNI on && kni_primary").  The same
+ * hand-off routine as yrss_route_burst, which sorts these classes on the host
+ * from q and filter where this call is given them by the kernel: list walks,
  * ARP clones in packet order (queue order inside a packet, then the KNI
  * clone), one enqueue per ring merged by index with the successful clones,
  * release of the refused tail and of the freed class, out_local = local class
@@ -507,7 +508,9 @@ struct yrss_route_result {
 
 /* process_packets(port, queue_id, mbufs, n, ctx, pkts_from_ring=0) with the
  * dispatcher registered (ff_dpdk_if.c:1058-1140), for a whole burst: classify
- * on the GPU (queue + protocol_filter), then per packet in order
+ * on the GPU (queue + protocol_filter), sort the packets by route class on the
+ * host (any nb_queues) and run the list hand-off of yrss_route_lists, whose
+ * outcome is, packet by packet in order,
  *   ret < 0 || ret >= nb_queues        -> release (:1080-1083)
  *   ret != queue_id                    -> ring[ret], FIFO; release if full (:1087-1093)
  *   local, FILTER_ARP                  -> clone to every other queue's ring, a KNI

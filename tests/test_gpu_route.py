@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from frames import ipv4_frame
+from route_helpers import Rings
 from test_gpu_parity import _fake_mbufs, to_np
 from test_kni_oracle import ipip_frame
 
@@ -93,37 +94,15 @@ def test_set_kni_rejects_bad_method():
         eng.set_kni(False, None, None, None)
 
 
-class Rings:
-    """Callback side of yrss_route_burst: bounded FIFO rings + clone pool."""
-
-    def __init__(self, addr_to_idx, capacity, clone_ok):
-        self.addr_to_idx = addr_to_idx
-        self.free = list(capacity)
-        self.rings = {j: [] for j in range(len(capacity))}
-        self.clone_ok = clone_ok
-        self.clones = {}
-        self.next_clone = 0x7F0000000000
-        self.released = []
-
-    def obj(self, a):
-        return self.clones[a] if a in self.clones else ("pkt", self.addr_to_idx[a])
-
-    def enqueue(self, queue, objs):
-        k = min(self.free[queue], len(objs))
-        self.rings[queue] += [self.obj(a) for a in objs[:k]]
-        self.free[queue] -= k
-        return k
-
-    def clone(self, m, queue):
-        i = self.addr_to_idx[m]
-        if not self.clone_ok(i, queue):
-            return 0
-        self.next_clone += 64
-        self.clones[self.next_clone] = ("clone", i, queue)
-        return self.next_clone
-
-    def release(self, m):
-        self.released.append(self.obj(m))
+def _fuzz_frames(oracle_mod, n):
+    """The SYN_FUZZ stream as frames of their stated length (at most 2048 bytes)."""
+    win, lens = oracle_mod.synth(abi.SYN_FUZZ, n, 5, stride=80)
+    frames = []
+    for i in range(n):
+        L = min(int(lens[i]), 2048)
+        f = win[i * 80:(i + 1) * 80].tobytes()
+        frames.append((f + bytes(max(0, L - 80)))[:L])
+    return frames
 
 
 @pytest.mark.parametrize("queue_id", [0, 1])
@@ -132,12 +111,7 @@ class Rings:
 @pytest.mark.parametrize("n", [3000, 6000])   # one-launch small path / multi-kernel path
 def test_route_burst_vs_process_packets(oracle_mod, queue_id, kni, cap, n):
     nq = 4
-    win, lens = oracle_mod.synth(abi.SYN_FUZZ, n, 5, stride=80)
-    frames = []
-    for i in range(n):
-        L = min(int(lens[i]), 2048)
-        f = win[i * 80:(i + 1) * 80].tobytes()
-        frames.append((f + bytes(max(0, L - 80)))[:L])
+    frames = _fuzz_frames(oracle_mod, n)
     pool, ptrs, stride = _fake_mbufs(frames)
     addr_to_idx = {int(a): i for i, a in enumerate(ptrs)}
     clone_ok = lambda i, j: (i * 7 + j) % 5 != 0          # noqa: E731 — some clones fail
@@ -161,6 +135,48 @@ def test_route_burst_vs_process_packets(oracle_mod, queue_id, kni, cap, n):
     assert [cb.obj(a) for a in kni_list] == kni_ref
     assert sorted(cb.released) == sorted(freed_ref)
     assert res.n_freed == len(freed_ref)
+    assert res.n_unresolved == sum(1 for o in local_ref if f_ref[o[1]] in (-2, -3))
+    assert [res.n_ring[j] for j in range(nq)] == [len(rings_ref[j]) for j in range(nq)]
+
+
+@pytest.mark.parametrize("queue_id", [0, 69, 70])     # 70: no local queue
+@pytest.mark.parametrize("method", ["accept", "reject"])
+def test_route_burst_above_route_lists_cap(oracle_mod, queue_id, method):
+    """nb_queues 70, above YRSS_ROUTE_LISTS_MAX_QUEUES (the kernel's route
+    bucket limit, not the hand-off's): 600 packets, one launch over two full
+    and one partial 256-packet chunk; ring 2 (350 packets for 300 slots) fills."""
+    nq, n, cap = 70, 600, 300
+    frames = _fuzz_frames(oracle_mod, n)
+    pool, ptrs, stride = _fake_mbufs(frames)
+    addr_to_idx = {int(a): i for i, a in enumerate(ptrs)}
+    clone_ok = lambda i, j: (i * 7 + j) % 5 != 0          # noqa: E731 — some clones fail
+    tcp_ports, udp_ports = "0-30000", "20000-65535"
+    c = oracle_mod.cfg(80, nq, 1, 0)
+    tcp_bm, udp_bm = oracle_mod.kni_bitmap(tcp_ports), oracle_mod.kni_bitmap(udp_ports)
+    q_ref = [oracle_mod.toeplitz_dispatch(f, len(f), c)[0] for f in frames]
+    f_ref = [oracle_mod.protocol_filter(f, len(f), True, tcp_bm, udp_bm, avail=80)
+             for f in frames]
+    rings_ref, local_ref, kni_ref, freed_ref = oracle_mod.process_packets_route(
+        q_ref, f_ref, nq, queue_id, True, method == "accept", True, [cap] * nq, clone_ok)
+    # what the inputs cover: dropped q, a full ring, and on queue 0 (where the
+    # non-IP frames land) ARP clones in rings and KNI beside KNI packets
+    assert any(q >= nq for q in q_ref) and len(rings_ref[2 if queue_id != 2 else 0]) == cap
+    assert any(o[0] == "clone" for o in freed_ref) == (queue_id == 0)
+    if queue_id == 0:
+        assert any(o[0] == "clone" for r in rings_ref.values() for o in r)
+        assert {o[0] for o in kni_ref} == {"pkt", "clone"}
+        assert any(f_ref[o[1]] == abi.FILTER_ARP for o in local_ref)
+    assert bool(local_ref) == (queue_id < nq) and bool(kni_ref) == (queue_id < nq)
+    with SoftRss(80, nq, 1, 0, device=0) as eng:
+        eng.set_kni(True, method, tcp_ports, udp_ports)
+        cb = Rings(addr_to_idx, [cap] * nq, clone_ok)
+        local, kni_list, res = eng.route_burst(ptrs, queue_id, cb.enqueue, cb.clone, cb.release)
+    assert cb.rings == rings_ref
+    assert [cb.obj(a) for a in local] == local_ref
+    assert [cb.obj(a) for a in kni_list] == kni_ref
+    assert sorted(cb.released) == sorted(freed_ref)
+    assert (res.n_local, res.n_kni, res.n_freed) == (len(local_ref), len(kni_ref), len(freed_ref))
+    assert res.n_arp == sum(1 for o in local_ref if f_ref[o[1]] == abi.FILTER_ARP)
     assert res.n_unresolved == sum(1 for o in local_ref if f_ref[o[1]] in (-2, -3))
     assert [res.n_ring[j] for j in range(nq)] == [len(rings_ref[j]) for j in range(nq)]
 

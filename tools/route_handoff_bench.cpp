@@ -1,10 +1,13 @@
 // Host cost of process_packets' hand-off for one burst, on the CPU (no GPU):
 //   lists      yrss_route_lists on the routed lists (ridx, rstart) a route burst
 //              kernel wrote: list walks, reads neither q nor filter
-//   per-packet the decision yrss_route_burst makes after its classification,
-//              from q / filter / qidx / qstart (restated below from
-//              yastack_amd/csrc/yrss.hip, with its std::vector scratch)
-// Both drive the same callbacks (rings that append into preallocated arrays, a
+//   classified yrss_route_classified, what yrss_route_burst runs after its
+//              classification: route classes from q / filter, a stable counting
+//              sort into (ridx, rstart), then the same list walks
+//   per-packet the former body of yrss_route_burst, kept here as the baseline:
+//              the hand-off decided packet by packet from q / filter / qidx /
+//              qstart, with its std::vector scratch
+// All drive the same callbacks (rings that append into preallocated arrays, a
 // clone that hands out addresses, a release that counts), on the same random
 // burst: nb_queues 3, queue_id 2, KNI on ("accept"), a tenth of the local
 // packets ARP and a fifth KNI.  Reported: ns per packet, median [min-max] over
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "yrss.h"
+#include "../yastack_amd/csrc/yrss_route_internal.h"
 
 namespace {
 
@@ -60,7 +64,8 @@ void *cb_clone(void *user, void *m, uint16_t queue)
 }
 void cb_release(void *user, void *) { ((Sink *)user)->released++; }
 
-// yrss_route_burst after classify_staged / finish_burst
+// yrss_route_burst after classify_staged / finish_burst, as it was before it
+// called yrss_route_classified
 void per_packet(const int16_t *q, const int8_t *fc, const uint32_t *qidx, const uint32_t *qstart,
                 uint32_t nq, uint16_t queue_id, bool kni_enable, bool kni_accept, int kni_primary,
                 void *const *mbufs, const yrss_route_ops *ops, void **out_local, void **out_kni,
@@ -178,10 +183,10 @@ int main()
         lists(bkt, nq + 1, qidx, qstart);
         lists(rbk, nq + 3, ridx, rstart);
         const uint32_t reps = n == 32 ? 20000 : 1000;
-        std::vector<double> t[2];
-        yrss_route_result ra, rb;
+        std::vector<double> t[3];
+        yrss_route_result ra, rb, rc;
         for (uint32_t r = 0; r < rounds; ++r)
-            for (int leg : {(int)(r & 1u), (int)(~r & 1u)}) {
+            for (int leg : {(int)(r % 3u), (int)((r + 1u) % 3u), (int)((r + 2u) % 3u)}) {
                 const double t0 = now_ns();
                 for (uint32_t k = 0; k < reps; ++k) {
                     memset(sink.fill, 0, sizeof(sink.fill));
@@ -189,20 +194,26 @@ int main()
                         if (yrss_route_lists(ridx.data(), rstart.data(), n, nq, queue_id, 1, nullptr,
                                              mb.data(), &ops, ol.data(), ok.data(), &ra))
                             return 1;
-                    } else {
+                    } else if (leg == 1) {
                         per_packet(q.data(), fc.data(), qidx.data(), qstart.data(), nq, queue_id,
                                    true, true, 1, mb.data(), &ops, ol.data(), ok.data(), &rb);
+                    } else {
+                        if (yrss_route_classified(q.data(), fc.data(), n, nq, queue_id, 1, 1, 1,
+                                                  mb.data(), &ops, ol.data(), ok.data(), &rc))
+                            return 1;
                     }
                 }
                 t[leg].push_back((now_ns() - t0) / reps / n);
             }
-        if (ra.n_local != rb.n_local || ra.n_kni != rb.n_kni || ra.n_freed != rb.n_freed ||
-            ra.n_arp != rb.n_arp || memcmp(ra.n_ring, rb.n_ring, sizeof(ra.n_ring))) {
-            fprintf(stderr, "the two hand-offs disagree\n");
-            return 1;
-        }
-        const char *name[2] = {"yrss_route_lists (routed lists)", "per-packet (q/filter/qidx)  "};
-        for (int leg = 0; leg < 2; ++leg) {
+        for (const yrss_route_result *o : {&rb, &rc})
+            if (ra.n_local != o->n_local || ra.n_kni != o->n_kni || ra.n_freed != o->n_freed ||
+                ra.n_arp != o->n_arp || memcmp(ra.n_ring, o->n_ring, sizeof(ra.n_ring))) {
+                fprintf(stderr, "the hand-offs disagree\n");
+                return 1;
+            }
+        const char *name[3] = {"yrss_route_lists (routed lists)", "per-packet (q/filter/qidx)     ",
+                               "yrss_route_classified (q/filter)"};
+        for (int leg = 0; leg < 3; ++leg) {
             std::sort(t[leg].begin(), t[leg].end());
             printf("n %4u  %s  %6.2f ns/pkt median [%.2f-%.2f] over %u rounds of %u bursts\n", n,
                    name[leg], t[leg][t[leg].size() / 2], t[leg].front(), t[leg].back(), rounds,

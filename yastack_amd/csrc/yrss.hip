@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "yrss.h"
+#include "yrss_route_internal.h"
 #include "yrss_synth.h"
 #ifdef YRSS_TEST_HOOKS
 #include "yrss_test_hooks.h"
@@ -5027,6 +5028,8 @@ int yrss_route_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, uint16_t queue
         return rc;
     std::vector<int16_t> q(n);
     std::vector<int8_t> fc(n);
+    // (the per-queue lists are not read here; asking for them keeps the launch
+    // what it has always been)
     std::vector<uint32_t> qidx(n), qstart(c->nb + 1);
     rc = classify_staged(c, n, W, q.data(), nullptr, qidx.data(), qstart.data(), fc.data(),
                          false);
@@ -5034,86 +5037,11 @@ int yrss_route_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, uint16_t queue
         rc = finish_burst(c);
     if (rc)
         return rc;
-    const uint32_t nq = c->cfg.nb_queues;
-    const bool local_ok = queue_id < nq;
-
-    // ARP packets kept on this lcore are deep-cloned to every other queue
-    // (ff_dpdk_if.c:1099-1119), in packet order, queue order inside a packet,
-    // then once more for KNI when enabled in the primary (:1123-1129).
-    std::vector<uint32_t> arp;               // packet indices, ascending
-    if (local_ok)
-        for (uint32_t k = qstart[queue_id]; k < qstart[queue_id + 1]; ++k)
-            if (fc[qidx[k]] == YRSS_FILTER_ARP)
-                arp.push_back(qidx[k]);
-    std::vector<void *> clones((size_t)arp.size() * nq, nullptr);
-    std::vector<void *> kni_clone(arp.size(), nullptr);
-    for (size_t a = 0; a < arp.size(); ++a) {
-        void *m = mbufs[arp[a]];
-        for (uint16_t j = 0; j < nq; ++j)
-            if (j != queue_id)
-                clones[a * nq + j] = ops->clone(ops->user, m, j);
-        if (c->kni_enable && kni_primary)
-            kni_clone[a] = ops->clone(ops->user, m, 0xFFFFu);
-    }
-
-    // One FIFO burst per ring: that queue's packets merged by packet index with
-    // the ARP clones (a failed clone enqueues nothing, :1114-1118).
-    std::vector<void *> objs;
-    for (uint16_t j = 0; j < nq; ++j) {
-        if (j == queue_id)
-            continue;
-        objs.clear();
-        uint32_t k = qstart[j];
-        const uint32_t e = qstart[j + 1];
-        size_t a = 0;
-        while (k < e || a < arp.size()) {
-            if (a < arp.size() && (k >= e || arp[a] < qidx[k])) {
-                if (clones[a * nq + j])
-                    objs.push_back(clones[a * nq + j]);
-                ++a;
-            } else {
-                objs.push_back(mbufs[qidx[k++]]);
-            }
-        }
-        unsigned done = objs.empty() ? 0u : ops->enqueue(ops->user, j, objs.data(),
-                                                         (unsigned)objs.size());
-        if (done > objs.size())
-            done = (unsigned)objs.size();
-        res->n_ring[j] = done;
-        for (size_t r = done; r < objs.size(); ++r) {      // ring full: free (:1090)
-            ops->release(ops->user, objs[r]);
-            res->n_freed++;
-        }
-    }
-    // ret < 0 || ret >= nb_queues: freed (:1080-1083)
-    for (uint32_t k = qstart[nq]; k < qstart[nq + 1]; ++k) {
-        ops->release(ops->user, mbufs[qidx[k]]);
-        res->n_freed++;
-    }
-    // Local packets, in order: protocol_filter decides (:1096-1138).
-    if (local_ok) {
-        size_t a = 0;
-        for (uint32_t k = qstart[queue_id]; k < qstart[queue_id + 1]; ++k) {
-            const uint32_t i = qidx[k];
-            const int f = fc[i];
-            if (f == YRSS_FILTER_ARP) {
-                if (kni_clone[a])
-                    out_kni[res->n_kni++] = kni_clone[a];
-                ++a;
-                out_local[res->n_local++] = mbufs[i];
-                res->n_arp++;
-            } else if (f == YRSS_FILTER_TRUNC || f == YRSS_FILTER_LOOP) {
-                out_local[res->n_local++] = mbufs[i];
-                res->n_unresolved++;
-            } else if (c->kni_enable && ((f == YRSS_FILTER_KNI && c->kni_accept) ||
-                                         (f == YRSS_FILTER_UNKNOWN && !c->kni_accept))) {
-                out_kni[res->n_kni++] = mbufs[i];
-            } else {
-                out_local[res->n_local++] = mbufs[i];
-            }
-        }
-    }
-    return 0;
+    // the hand-off itself: the one routine of yrss_route_seg / yrss_route_lists,
+    // over the route classes sorted out of q and fc (yrss_seg.cpp)
+    return yrss_route_classified(q.data(), fc.data(), n, c->cfg.nb_queues, queue_id,
+                                 c->kni_enable, c->kni_accept, kni_primary, mbufs, ops, out_local,
+                                 out_kni, res);
 }
 
 static void rss_check_params(const yrss_ctx *c, uint16_t nb_queues, uint16_t reta_size,

@@ -10,20 +10,24 @@
 // synchronised, so nothing read from them is used as an index before it is
 // checked.  yastack_amd/segments.py is the Python twin.
 //
+// process_packets' hand-off (ff_dpdk_if.c:1058-1140) is written once, here, as
+// walks over route-class lists (route_hand_off), and has three entries.
 // yrss_route_seg consumes the routed form of yrss_route_dev_seg (nb_queues + 3
-// route buckets a segment) and performs process_packets' hand-off
-// (ff_dpdk_if.c:1058-1140) with list walks alone: what yrss_route_burst decides
-// per packet from q and filter, the parse kernel has already decided.
-// yrss_route_lists does the same from the one global routed list of a host
-// burst or a route worker's burst (yrss_route_lists_*, yrss_worker_start_route);
-// both run the one hand-off routine, over 8-bit or 32-bit indices.
+// route buckets a segment), where the parse kernel has already decided every
+// packet's class.  yrss_route_lists does the same from the one global routed
+// list of a host burst or a route worker's burst (yrss_route_lists_*,
+// yrss_worker_start_route).  yrss_route_classified (yrss_route_internal.h, not
+// exported) is yrss_route_burst's: that call gets q and filter per packet from
+// the GPU, so the classes are sorted out of them here, for any nb_queues.
 #include <errno.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <new>
 
 #include "yrss.h"
+#include "yrss_route_internal.h"
 
 extern "C" {
 
@@ -108,8 +112,9 @@ static int route_seg_valid(const uint8_t *seg_idx, const uint16_t *seg_off, uint
 // process_packets' hand-off (ff_dpdk_if.c:1058-1140) over one set of finished
 // route lists: idx the packet indices (into m and, offset by first, into
 // filter) grouped by route class, o the nq + 4 offsets, already validated.
-// Shared by the segments of yrss_route_seg (8-bit indices, 16-bit offsets) and
-// the one global list of yrss_route_lists (32-bit both).  Scratch from the
+// Shared by the segments of yrss_route_seg (8-bit indices, 16-bit offsets), the
+// one global list of yrss_route_lists and the list yrss_route_classified sorts
+// for yrss_route_burst (32-bit both).  Scratch from the
 // caller: cl (ARP packets x nq clones), kc (one KNI clone per ARP packet),
 // burst (as many objects as one ring can be offered: packets + ARP packets).
 template <typename Idx, typename Off>
@@ -190,7 +195,63 @@ static void route_hand_off(const Idx *idx, const Off *o, void *const *m, uint32_
     }
 }
 
+// The host twin of the parse kernel's route_bucket (yrss.hip): what
+// process_packets does with a packet of queue q and filter class fc on the
+// lcore whose queue is queue_id, as a class below nq + 3: b < nq the ring of
+// queue b, or local delivery where b == queue_id; nq freed; nq + 1 KNI; nq + 2
+// ARP on the local queue.  queue_id >= nq: no local queue, classes <= nq only.
+static inline uint32_t route_class(int q, int fc, uint32_t nq, uint32_t queue_id, bool kni_enable,
+                                   bool kni_accept)
+{
+    if ((uint32_t)q >= nq)                 // q < 0 included
+        return nq;
+    if ((uint32_t)q != queue_id)
+        return (uint32_t)q;
+    if (fc == YRSS_FILTER_ARP)
+        return nq + 2u;
+    const bool kni = kni_enable && fc == (kni_accept ? YRSS_FILTER_KNI : YRSS_FILTER_UNKNOWN);
+    return kni ? nq + 1u : (uint32_t)q;
+}
+
 extern "C" {
+
+int yrss_route_classified(const int16_t *q, const int8_t *filter, uint32_t n, uint16_t nb_queues,
+                          uint16_t queue_id, int kni_enable, int kni_accept, int kni_primary,
+                          void *const *objs, const struct yrss_route_ops *ops, void **out_local,
+                          void **out_kni, struct yrss_route_result *res)
+{
+    if (!ops || !ops->enqueue || !ops->clone || !ops->release || !res)
+        return -EINVAL;
+    if (nb_queues < 1 || nb_queues > YRSS_MAX_QUEUES)
+        return -EINVAL;
+    if (n && (!q || !filter || !objs || !out_local || !out_kni))
+        return -EINVAL;
+    memset(res, 0, sizeof(*res));
+    if (n == 0)
+        return 0;
+    const uint32_t nq = nb_queues, nrb = nq + 3u;
+    // stable counting sort by class: counts (at b + 1) -> exclusive starts
+    uint32_t rstart[YRSS_MAX_QUEUES + 4] = {0}, cur[YRSS_MAX_QUEUES + 3];
+    for (uint32_t i = 0; i < n; ++i)
+        rstart[route_class(q[i], filter[i], nq, queue_id, kni_enable, kni_accept) + 1u]++;
+    for (uint32_t b = 0; b < nrb; ++b) {
+        rstart[b + 1] += rstart[b];
+        cur[b] = rstart[b];
+    }
+    // one allocation: route_hand_off's scratch as yrss_route_lists sizes it (the
+    // ARP packets' clones, one ring's burst), then the list
+    const size_t na = rstart[nq + 3u] - rstart[nq + 2u];
+    void **scratch = (void **)malloc((na * nq + na + n) * sizeof(void *) + n * sizeof(uint32_t));
+    if (!scratch)
+        return -ENOMEM;
+    uint32_t *ridx = (uint32_t *)(scratch + na * nq + na + n);
+    for (uint32_t i = 0; i < n; ++i)
+        ridx[cur[route_class(q[i], filter[i], nq, queue_id, kni_enable, kni_accept)]++] = i;
+    route_hand_off(ridx, rstart, objs, 0u, nq, queue_id, kni_enable && kni_primary, filter, ops,
+                   out_local, out_kni, res, scratch, scratch + na * nq, scratch + na * nq + na);
+    free(scratch);
+    return 0;
+}
 
 int yrss_route_seg(const uint8_t *seg_idx, const uint16_t *seg_off, uint32_t n,
                    uint16_t nb_queues, uint16_t queue_id, int kni_clone, const int8_t *filter,

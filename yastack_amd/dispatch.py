@@ -502,9 +502,19 @@ class SoftRss:
         (local list, kni list, RouteResult)."""
         mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
         n = int(mb.size)
+        return self._hand_off(
+            "yrss_route_burst", n, 2 * n, enqueue, clone, release,
+            lambda ops, local, kni, res: self._lib.yrss_route_burst(
+                self._ctx, _ptr(mb), n, queue_id, 1 if kni_primary else 0, ops, local, kni, res))
 
-        def _enq(user, queue, objs, cnt):
-            return int(enqueue(int(queue), [int(objs[i] or 0) for i in range(cnt)]))
+    @staticmethod
+    def _hand_off(name, n, kni_size, enqueue, clone, release, call):
+        """The callback shim of the three hand-off calls: ``call(ops, local,
+        kni, res)`` makes the C call ``name`` with the RouteOps built from the
+        Python callbacks (the thunks live until it returns), a local list of n
+        and a KNI list of ``kni_size`` addresses."""
+        def _enq(user, queue, ptrs, cnt):
+            return int(enqueue(int(queue), [int(ptrs[i] or 0) for i in range(cnt)]))
 
         def _clone(user, m, queue):
             return int(clone(int(m or 0), int(queue)) or 0)
@@ -514,12 +524,9 @@ class SoftRss:
 
         ops = abi.RouteOps(abi.ENQUEUE_FN(_enq), abi.CLONE_FN(_clone), abi.RELEASE_FN(_rel), None)
         local = np.zeros(max(n, 1), np.uint64)
-        kni = np.zeros(max(2 * n, 1), np.uint64)
+        kni = np.zeros(max(kni_size, 1), np.uint64)
         res = abi.RouteResult()
-        rc = self._lib.yrss_route_burst(self._ctx, _ptr(mb), n, queue_id, 1 if kni_primary else 0,
-                                        ctypes.byref(ops), _ptr(local), _ptr(kni),
-                                        ctypes.byref(res))
-        abi.check(rc, "yrss_route_burst")
+        abi.check(call(ctypes.byref(ops), _ptr(local), _ptr(kni), ctypes.byref(res)), name)
         return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
 
     def _route_lists_out(self, n, want_hash, want_filter):
@@ -589,25 +596,12 @@ class SoftRss:
                 (filt is not None and filt.size < n):
             raise ValueError("arrays shorter than the burst")
 
-        def _enq(user, queue, ptrs, cnt):
-            return int(enqueue(int(queue), [int(ptrs[i] or 0) for i in range(cnt)]))
-
-        def _clone(user, m, queue):
-            return int(clone(int(m or 0), int(queue)) or 0)
-
-        def _rel(user, m):
-            release(int(m or 0))
-
-        ops = abi.RouteOps(abi.ENQUEUE_FN(_enq), abi.CLONE_FN(_clone), abi.RELEASE_FN(_rel), None)
-        local = np.zeros(max(n, 1), np.uint64)
-        kni = np.zeros(max(n, 1), np.uint64)
-        res = abi.RouteResult()
-        rc = self._lib.yrss_route_lists(_ptr(ridx), _ptr(rstart), n, self.nb_queues, queue_id,
-                                        1 if self._kni_enable and kni_primary else 0, _ptr(filt),
-                                        _ptr(mb), ctypes.byref(ops), _ptr(local), _ptr(kni),
-                                        ctypes.byref(res))
-        abi.check(rc, "yrss_route_lists")
-        return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
+        kni_clone = 1 if self._kni_enable and kni_primary else 0
+        return self._hand_off(
+            "yrss_route_lists", n, n, enqueue, clone, release,
+            lambda ops, local, kni, res: self._lib.yrss_route_lists(
+                _ptr(ridx), _ptr(rstart), n, self.nb_queues, queue_id, kni_clone, _ptr(filt),
+                _ptr(mb), ops, local, kni, res))
 
     def route_seg(self, result_or_arrays, objs, queue_id: int, enqueue, clone, release,
                   kni_primary: bool = True):
@@ -637,25 +631,12 @@ class SoftRss:
                 (filt is not None and filt.size < n):
             raise ValueError("arrays shorter than the batch")
 
-        def _enq(user, queue, ptrs, cnt):
-            return int(enqueue(int(queue), [int(ptrs[i] or 0) for i in range(cnt)]))
-
-        def _clone(user, m, queue):
-            return int(clone(int(m or 0), int(queue)) or 0)
-
-        def _rel(user, m):
-            release(int(m or 0))
-
-        ops = abi.RouteOps(abi.ENQUEUE_FN(_enq), abi.CLONE_FN(_clone), abi.RELEASE_FN(_rel), None)
-        local = np.zeros(max(n, 1), np.uint64)
-        kni = np.zeros(max(n, 1), np.uint64)
-        res = abi.RouteResult()
-        rc = self._lib.yrss_route_seg(_ptr(seg_idx), _ptr(seg_off), n, self.nb_queues, queue_id,
-                                      1 if self._kni_enable and kni_primary else 0, _ptr(filt),
-                                      _ptr(mb), ctypes.byref(ops), _ptr(local), _ptr(kni),
-                                      ctypes.byref(res))
-        abi.check(rc, "yrss_route_seg")
-        return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
+        kni_clone = 1 if self._kni_enable and kni_primary else 0
+        return self._hand_off(
+            "yrss_route_seg", n, n, enqueue, clone, release,
+            lambda ops, local, kni, res: self._lib.yrss_route_seg(
+                _ptr(seg_idx), _ptr(seg_off), n, self.nb_queues, queue_id, kni_clone, _ptr(filt),
+                _ptr(mb), ops, local, kni, res))
 
     # -- connect-side RSS check (ff_rss_check) -------------------------------
     def rss_check_dev(self, tuples, nb_queues: int, reta_size: int, queueid: int, stream=None):

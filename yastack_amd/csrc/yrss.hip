@@ -3444,6 +3444,31 @@ ParseKernel pick_parse(int count, bool filter)
                       : yrss_parse_hash<0, false, kParseBlock>;
 }
 
+// The ParseParams every launch starts from: the context's constants (c->proto:
+// key schedule, modulo constants, nq and nb; every other field zero since
+// yrss_init), the fault record, the KNI state and, for a route launch
+// (route_lq >= 0), the nb_queues + 3 route classes of the lcore whose queue is
+// route_lq.  The caller adds only its own pointers and layout fields.
+// out16: full output bursts as 16-byte write-through stores: 1 for the grid
+// launches, whose four-tile bursts they were measured on
+// (profiles/r01_v13_ahead_out16_ab.log); 0 for the one-launch kernel and the
+// worker, which flush tile by tile, mostly into host memory, and keep the
+// lane-granular stores (the worker kernel clears it itself as well).
+ParseParams parse_params(const yrss_ctx *c, int route_lq, bool out16)
+{
+    ParseParams P = c->proto;
+    P.fault = c->d_fault_rec;
+    P.kni_bm = c->d_kni;
+    P.kni_enable = c->kni_enable ? 1u : 0u;
+    P.out16 = out16 ? 1u : 0u;
+    if (route_lq >= 0) {
+        P.nb = c->nb + 2u;
+        P.route_lq = (uint16_t)route_lq;
+        P.route_accept = c->kni_accept ? 1 : 0;
+    }
+    return P;
+}
+
 hipEvent_t take_event(yrss_ctx *c)
 {
     if (c->ev_free.empty()) {
@@ -3739,29 +3764,25 @@ bool small_ok(const yrss_ctx *c, uint32_t n)
     return c->tune.one_launch != 2 && n >= 1 && n <= kSmallMaxPkts && c->nb <= kSmallMaxNb;
 }
 
-// One launch of yrss_burst_small on the context stream.  S.P.win/len and the
-// output pointers are filled by the caller; this adds the configuration.
+// The parameters of one yrss_burst_small launch: all zero (no gather, no
+// lists, every layout field of the grid launches) but the configuration.
+// route_lq >= 0: the route instantiation over nq + 3 classes.
+SmallParams small_params(const yrss_ctx *c, int route_lq = -1)
+{
+    SmallParams S;
+    memset(&S, 0, sizeof(S));
+    S.P = parse_params(c, route_lq, false);
+    return S;
+}
+
+// One launch of yrss_burst_small, S from small_params with the caller's
+// windows and output pointers (route: S.qidx / S.qstart the routed lists).
 // host_burst: a host-resident burst on the context stream, completed by the
 // host spinning on the kernel's completion word; otherwise a device batch on
 // the caller's stream (no completion word).
-// route: the route instantiation over nq + 3 classes (S.P.route_lq set by the
-// caller; the KNI rule is the context's), S.qidx / S.qstart the routed lists.
 int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = true,
                  hipStream_t stream = nullptr, bool route = false)
 {
-    const ParseParams &proto = c->proto;
-    ParseParams &P = S.P;
-    memcpy(P.kwin, proto.kwin, sizeof(P.kwin));
-    P.nq = proto.nq;
-    P.nb = proto.nb;
-    P.mod_d = proto.mod_d;
-    P.q_off = proto.q_off;
-    P.mod_m = proto.mod_m;
-    P.seg_cnt = nullptr;
-    P.rank = nullptr;
-    P.fault = c->d_fault_rec;
-    P.kni_bm = c->d_kni;
-    P.kni_enable = c->kni_enable ? 1u : 0u;
     if (host_burst) {
         S.done = c->dh_done;
         S.seq = ++c->done_seq;
@@ -3770,11 +3791,7 @@ int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = tru
     } else {
         S.done = nullptr;
     }
-    if (route) {
-        P.nb = proto.nb + 2u;
-        P.route_accept = c->kni_accept ? 1 : 0;
-    }
-    const size_t lds = small_lds(P.nb, filter || route);
+    const size_t lds = small_lds(S.P.nb, filter || route);
     const dim3 grid(1);
     if (route)
         hipLaunchKernelGGL((yrss_burst_small<true, true>), grid, dim3(kSmallBlock), lds, stream, S);
@@ -3827,6 +3844,88 @@ int finish_burst(yrss_ctx *c)
     return 0;
 }
 
+// Device-visible alias of host bytes [p, p+bytes) if they lie in a registered
+// range (the first that contains them), else nullptr.
+inline const void *dev_alias(const yrss_ctx *c, const void *p, size_t bytes)
+{
+    const uint64_t a = (uint64_t)(uintptr_t)p;
+    for (uint32_t r = 0; r < c->nranges; ++r)
+        if (a >= c->ranges[r].lo && a + bytes <= c->ranges[r].hi)
+            return (const void *)(uintptr_t)(a + c->ranges[r].delta);
+    return nullptr;
+}
+
+// The configuration half of GatherParams: where the mbuf's fields sit and the
+// registered ranges as the context holds them now.
+void gather_config(const yrss_ctx *c, GatherParams &G)
+{
+    const yrss_mbuf_layout &ml = c->cfg.mbuf;
+    G.nranges = c->nranges;
+    G.off_buf_addr = ml.off_buf_addr;
+    G.off_data_off = ml.off_data_off;
+    G.off_data_len = ml.off_data_len;
+    G.off_hash_rss = ml.off_hash_rss;
+    memcpy(G.ranges, c->ranges, sizeof(G.ranges));
+}
+
+// Makes the context's pending burst that of n packets with the caller's host
+// arrays (NULL = not wanted; the lists only as a pair) and noff offsets, every
+// output through the pinned staging.  The caller marks it active once queued.
+PendingBurst &pend_setup(yrss_ctx *c, uint32_t n, int16_t *out_q, uint32_t *out_hash,
+                         uint32_t *out_qidx, uint32_t *out_qstart, int8_t *out_filter,
+                         uint32_t noff)
+{
+    const bool compact = out_qidx && out_qstart;
+    PendingBurst &p = c->pend;
+    p = PendingBurst{};
+    p.n = n;
+    p.outs[0] = {out_q, c->h_q, (size_t)n * 2, false};
+    p.outs[1] = {out_hash, c->h_hash, (size_t)n * 4, false};
+    p.outs[2] = {compact ? out_qidx : nullptr, c->h_qidx, (size_t)n * 4, false};
+    p.outs[3] = {compact ? out_qstart : nullptr, c->h_qstart, (size_t)noff * 4, false};
+    p.outs[4] = {out_filter, c->h_filter, n, false};
+    return p;
+}
+
+// The multi-launch path of the pending host burst: the device batch over the
+// context's device staging (the windows are there at stride W), hash wanted or
+// not, the lists and the filter class as the pending burst asks for them.
+int staged_dev_batch(yrss_ctx *c, uint32_t W, bool want_hash)
+{
+    const PendingBurst &p = c->pend;
+    const bool compact = p.outs[2].user != nullptr;
+    yrss_dev_batch b;
+    b.win = c->d_win;
+    b.win_stride = W;
+    b.n = p.n;
+    b.len = c->d_len;
+    b.q = c->d_q;
+    b.hash = want_hash ? c->d_hash : nullptr;
+    b.qidx = compact ? c->d_qidx : nullptr;
+    b.qstart = compact ? c->d_qstart : nullptr;
+    b.filter = p.outs[4].user ? c->d_filter : nullptr;
+    return dispatch_dev_impl(c, &b, c->stream);
+}
+
+// ... and its outputs back from the device staging, each into the caller's
+// array where that is registered (direct), else into the pinned staging;
+// stage_hash: the hash too when the caller has no array for it (the host-side
+// hash.rss write-back reads the staging).  The burst is queued with this.
+int staged_copy_back(yrss_ctx *c, bool stage_hash)
+{
+    PendingBurst &p = c->pend;
+    const void *src[5] = {c->d_q, c->d_hash, c->d_qidx, c->d_qstart, c->d_filter};
+    for (int k = 0; k < 5; ++k) {
+        if (!p.outs[k].user && !(k == 1 && stage_hash))
+            continue;
+        YRSS_HIP(hipMemcpyAsync(p.outs[k].direct ? p.outs[k].user : p.outs[k].stage, src[k],
+                                p.outs[k].bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    p.dev_fault = p.outs[2].user != nullptr;   // the lists' guards
+    p.active = true;
+    return 0;
+}
+
 // Queues the classification of windows already gathered into c->h_win /
 // c->h_len at stride W; results go to the caller's host arrays (NULL = not
 // wanted) when the burst completes (finish_burst).  want_hash computes the
@@ -3840,21 +3939,13 @@ int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_
 {
     const bool route = route_lq >= 0;
     hipStream_t s = c->stream;
-    const bool compact = out_qidx && out_qstart;
     want_hash = want_hash || out_hash;
-    PendingBurst &p = c->pend;
-    p = PendingBurst{};
-    p.n = n;
-    p.outs[0] = {out_q, c->h_q, (size_t)n * 2, false};
-    p.outs[1] = {out_hash, c->h_hash, (size_t)n * 4, false};
-    p.outs[2] = {compact ? out_qidx : nullptr, c->h_qidx, (size_t)n * 4, false};
-    p.outs[3] = {compact ? out_qstart : nullptr, c->h_qstart, (c->nb + (route ? 3 : 1)) * 4,
-                 false};
-    p.outs[4] = {out_filter, c->h_filter, n, false};
+    PendingBurst &p = pend_setup(c, n, out_q, out_hash, out_qidx, out_qstart, out_filter,
+                                 c->nb + (route ? 3u : 1u));
+    const bool compact = p.outs[2].user != nullptr;
     if (route || small_ok(c, n)) {
         // the kernel reads the staged windows and writes the staging in place
-        SmallParams S;
-        memset(&S, 0, sizeof(S));
+        SmallParams S = small_params(c, route_lq);
         S.P.win = c->dh_win;
         S.P.len = c->dh_len;
         S.P.stride = W;
@@ -3864,7 +3955,6 @@ int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_
         S.P.filter = out_filter ? c->dh_filter : nullptr;
         S.qidx = compact ? c->dh_qidx : nullptr;
         S.qstart = compact ? c->dh_qstart : nullptr;
-        S.P.route_lq = route ? (uint16_t)route_lq : 0;
         int rc = small_launch(c, S, out_filter != nullptr, true, nullptr, route);
         if (rc)
             return rc;
@@ -3873,32 +3963,8 @@ int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_
     }
     YRSS_HIP(hipMemcpyAsync(c->d_win, c->h_win, (size_t)n * W, hipMemcpyHostToDevice, s));
     YRSS_HIP(hipMemcpyAsync(c->d_len, c->h_len, (size_t)n * 2, hipMemcpyHostToDevice, s));
-    yrss_dev_batch b;
-    b.win = c->d_win;
-    b.win_stride = W;
-    b.n = n;
-    b.len = c->d_len;
-    b.q = c->d_q;
-    b.hash = want_hash ? c->d_hash : nullptr;
-    b.qidx = compact ? c->d_qidx : nullptr;
-    b.qstart = compact ? c->d_qstart : nullptr;
-    b.filter = out_filter ? c->d_filter : nullptr;
-    int rc = dispatch_dev_impl(c, &b, s);
-    if (rc)
-        return rc;
-    YRSS_HIP(hipMemcpyAsync(c->h_q, c->d_q, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-    if (want_hash)
-        YRSS_HIP(hipMemcpyAsync(c->h_hash, c->d_hash, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    if (out_filter)
-        YRSS_HIP(hipMemcpyAsync(c->h_filter, c->d_filter, n, hipMemcpyDeviceToHost, s));
-    if (compact) {
-        YRSS_HIP(hipMemcpyAsync(c->h_qidx, c->d_qidx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        YRSS_HIP(hipMemcpyAsync(c->h_qstart, c->d_qstart, (c->nb + 1) * 4,
-                                hipMemcpyDeviceToHost, s));
-    }
-    p.dev_fault = compact;
-    p.active = true;
-    return 0;
+    int rc = staged_dev_batch(c, W, want_hash);
+    return rc ? rc : staged_copy_back(c, want_hash);
 }
 
 // Host entry points: one burst in flight per context.  begin_burst refuses a
@@ -3977,6 +4043,13 @@ int gather_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len, 
     return 0;
 }
 
+// The empty burst: no bucket of the nbk holds a packet, nbk + 1 offsets of 0.
+void zero_offsets(uint32_t *off, uint32_t nbk)
+{
+    if (off)
+        memset(off, 0, (nbk + 1u) * sizeof(uint32_t));
+}
+
 // yrss_route_lists_burst / _frames: what is refused before anything is
 // touched, and the empty burst.  1: done (n == 0), 0: go on, < 0: refused.
 int route_lists_begin(yrss_ctx *c, uint32_t n, const void *src, const void *src2,
@@ -3987,10 +4060,38 @@ int route_lists_begin(yrss_ctx *c, uint32_t n, const void *src, const void *src2
     if (n > kSmallMaxPkts || c->cfg.nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
         return -ENOTSUP;
     if (n == 0) {
-        memset(out_rstart, 0, (c->nb + 3u) * sizeof(uint32_t));
+        zero_offsets(out_rstart, c->nb + 2u);
         return 1;
     }
-    return begin_burst(c);
+    return 0;
+}
+
+// The staged entry points from the gather on: one burst at a time; the
+// headers of the mbufs src, or of the frames (src, len) when len is given,
+// gathered into the pinned staging and classified (classify_staged);
+// YRSS_F_WRITE_RSS (mbufs) keeps the hashes and the mbufs for the host-side
+// write-back; completed here unless YRSS_F_ASYNC.
+int staged_burst(yrss_ctx *c, const void *src, const uint16_t *len, uint32_t n, int16_t *out_q,
+                 uint32_t *out_hash, uint32_t *out_qidx, uint32_t *out_qstart, int8_t *out_filter,
+                 int route_lq, uint32_t flags)
+{
+    int rc = begin_burst(c);
+    if (rc)
+        return rc;
+    YRSS_HIP(hipSetDevice(c->device));
+    void *const *mbufs = len ? nullptr : (void *const *)src;
+    uint32_t W = 0;
+    rc = len ? gather_frames(c, (const uint8_t *const *)src, len, n, &W)
+             : gather_mbufs(c, mbufs, n, &W);
+    if (rc)
+        return rc;
+    const bool wb = mbufs && (flags & YRSS_F_WRITE_RSS) != 0;
+    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_qidx, out_qstart, out_filter, wb,
+                              route_lq)) != 0)
+        return rc;
+    if (wb)
+        c->pend.wb_mbufs = mbufs;
+    return end_burst(c, flags);
 }
 
 }  // namespace
@@ -4076,7 +4177,6 @@ int yrss_init(const struct yrss_config *cfg, yrss_ctx **out)
     c->device = cfg->device;
     c->cus = prop.multiProcessorCount;
     c->tune.scatter_xcd = -1;
-    c->proto.out16 = 1;   // 16-byte write-through bursts (profiles/r01_v13_ahead_out16_ab.log)
     c->nb = (uint32_t)cfg->nb_queues + 1u;
     compute_key_schedule(cfg, c->proto.kwin);
     const bool only = cfg->soft_dispatch && cfg->dispatch_only_core;
@@ -4084,11 +4184,9 @@ int yrss_init(const struct yrss_config *cfg, yrss_ctx **out)
     c->proto.q_off = only ? 1u : 0u;
     c->proto.mod_m = UINT64_MAX / c->proto.mod_d + 1u;   // wraps to 0 for d == 1
     c->proto.nq = cfg->nb_queues;
-    c->proto.nb = c->nb;
+    c->proto.nb = c->nb;   // (every other field stays zero: parse_params)
 
-    const size_t ws = (size_t)kMaxChunks * c->nb * sizeof(uint32_t);
     hipError_t e;
-    (void)ws;
     if ((e = list_ws_alloc(c, c->ws)) != hipSuccess ||
         (e = hipHostMalloc((void **)&c->d_fault_rec, 64, hipHostMallocCoherent)) != hipSuccess ||
         (e = hipMalloc((void **)&c->d_kni, sizeof(c->kni_bm))) != hipSuccess ||
@@ -4231,19 +4329,74 @@ int yrss_dispatch_dev_ex(yrss_ctx *c, const struct yrss_dev_batch *b, void *stre
 
 namespace {
 
+// A list output of a device batch and the alignment it needs (a mask).
+struct ListBuf {
+    const void *p;
+    uintptr_t mask;
+};
+
+// What every device batch has to satisfy, all of it -EINVAL: the window
+// stride, at most max_n packets, the arrays a batch that is not empty needs
+// (its two list outputs too where the form has no variant without them) and
+// every pointer's alignment.
+int check_dev_batch(const void *win, uint32_t stride, const void *len, uint32_t n, uint32_t max_n,
+                    const void *q, const void *hash, ListBuf idx, ListBuf off, bool need_lists)
+{
+    if (stride < YRSS_WIN_MIN || (stride & 15u) || n > max_n)
+        return -EINVAL;
+    if (n && (!win || !len || !q || (need_lists && (!idx.p || !off.p))))
+        return -EINVAL;
+    if (((uintptr_t)win & 15u) || ((uintptr_t)len & 1u) || ((uintptr_t)q & 1u) ||
+        ((uintptr_t)hash & 3u) || ((uintptr_t)idx.p & idx.mask) || ((uintptr_t)off.p & off.mask))
+        return -EINVAL;
+    return 0;
+}
+
+// A device batch takes the context over on stream s.  This context's resident
+// worker holds CUs the batch's full grid needs: it is retired first (published
+// tickets stay in the ring; the next worker submit or poll relaunches).  The
+// workspace, the fault record and the timing events are shared by every
+// dispatch of the context: s waits for what the last batch's stream holds.
+int take_stream(yrss_ctx *c, hipStream_t s)
+{
+    const int rc = worker_halt(c);   // (nothing unless one is running)
+    if (rc)
+        return rc;
+    if (c->last_stream_valid && c->last_stream != s) {
+        YRSS_HIP(hipEventRecord(c->switch_ev, c->last_stream));
+        YRSS_HIP(hipStreamWaitEvent(s, c->switch_ev, 0));
+    }
+    c->last_stream = s;
+    c->last_stream_valid = true;
+    return 0;
+}
+
+typedef void (*LineKernel)(LineParams);
+
+// The line scatter for a plan (pick_parse's counterpart): the bucket packed
+// beside the rank or read from q, kG = groups (2 or 4), non-temporal list
+// stores (nt) past kListNtBuckets buckets.  (It stands here, not beside
+// pick_parse: the kernels' order in the code object follows their first use.)
+LineKernel pick_lines(bool packed, uint32_t groups, bool nt)
+{
+    if (groups == 4u) {
+        if (packed)
+            return nt ? yrss_scatter_lines<true, 4, true> : yrss_scatter_lines<true, 4, false>;
+        return nt ? yrss_scatter_lines<false, 4, true> : yrss_scatter_lines<false, 4, false>;
+    }
+    if (packed)
+        return nt ? yrss_scatter_lines<true, 2, true> : yrss_scatter_lines<true, 2, false>;
+    return nt ? yrss_scatter_lines<false, 2, true> : yrss_scatter_lines<false, 2, false>;
+}
+
 int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
 {
     const uint32_t n = b->n, win_stride = b->win_stride;
-    if (win_stride < YRSS_WIN_MIN || (win_stride & 15u) || n > YRSS_MAX_BATCH)
-        return -EINVAL;
-    if (n && (!b->win || !b->len || !b->q))
-        return -EINVAL;
-    if (((uintptr_t)b->win & 15u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->q & 1u) ||
-        ((uintptr_t)b->hash & 3u) || ((uintptr_t)b->qidx & 3u) || ((uintptr_t)b->qstart & 3u))
-        return -EINVAL;
     const bool compact = b->qidx != nullptr;
     const bool filter = b->filter != nullptr;
-    if (compact && !b->qstart)
+    if (check_dev_batch(b->win, win_stride, b->len, n, YRSS_MAX_BATCH, b->q, b->hash,
+                        {b->qidx, 3u}, {b->qstart, 3u}, false) != 0 ||
+        (compact && !b->qstart))
         return -EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
@@ -4251,28 +4404,14 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
             YRSS_HIP(hipMemsetAsync(b->qstart, 0, (c->nb + 1) * sizeof(uint32_t), s));
         return 0;
     }
-    // This context's resident worker holds CUs the batch's full grid needs:
-    // retire it first (published tickets stay in the ring; the next worker
-    // submit or poll relaunches).
-    if (c->w.running) {
-        const int rc = worker_halt(c);
-        if (rc)
-            return rc;
-    }
-
-    if (c->last_stream_valid && c->last_stream != s) {
-        YRSS_HIP(hipEventRecord(c->switch_ev, c->last_stream));
-        YRSS_HIP(hipStreamWaitEvent(s, c->switch_ev, 0));
-    }
-    c->last_stream = s;
-    c->last_stream_valid = true;
+    if (const int rc = take_stream(c, s))
+        return rc;
     // Up to 4096 packets: one launch of the one-workgroup burst kernel (parse,
     // lists in LDS) instead of parse + scan + scatter, ~10 us less per call
     // (profiles/r01_v26_small_kernel_stats.csv: three launches cost >= 15 us of
     // kernel time however small the batch).  Not timed by yrss_timing_*.
     if (small_ok(c, n) && c->tune.one_launch == 0) {
-        SmallParams S;
-        memset(&S, 0, sizeof(S));
+        SmallParams S = small_params(c);
         S.P.win = b->win;
         S.P.len = b->len;
         S.P.stride = win_stride;
@@ -4316,20 +4455,11 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     // in-scatter prefixes (up to kFusedMaxNb buckets) the parse kernel sums
     // the totals and no scan kernel runs.  Fused when the range table fits
     // without costing the scatter a resident workgroup.
-    void (*line_fn)(LineParams) = nullptr;
+    LineKernel line_fn = nullptr;
     uint32_t line_grid = 0, line_lds_bytes = lp.lds, rts = 0, rcs = 0;
     bool fused = false;
     if (ranked) {
-        const bool nt = c->nb > kListNtBuckets;
-        line_fn = lp.groups == 4u
-                      ? (lp.packed ? (nt ? yrss_scatter_lines<true, 4, true>
-                                         : yrss_scatter_lines<true, 4, false>)
-                                   : (nt ? yrss_scatter_lines<false, 4, true>
-                                         : yrss_scatter_lines<false, 4, false>))
-                      : (lp.packed ? (nt ? yrss_scatter_lines<true, 2, true>
-                                         : yrss_scatter_lines<true, 2, false>)
-                                   : (nt ? yrss_scatter_lines<false, 2, true>
-                                         : yrss_scatter_lines<false, 2, false>));
+        line_fn = pick_lines(lp.packed, lp.groups, c->nb > kListNtBuckets);
         // persistent: the resident workgroups, each one contiguous range of
         // spans, never more workgroups than spans
         const uint32_t spans = (uint32_t)(((uint64_t)n + lp.seg - 1) / lp.seg);
@@ -4352,14 +4482,13 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
             }
         }
     }
-    ParseParams P = c->proto;
+    ParseParams P = parse_params(c, -1, true);
     P.win = b->win;
     P.len = b->len;
     P.q = b->q;
     P.hash = b->hash;
     P.seg_cnt = compact ? W.seg_cnt : nullptr;
     P.rank = ranked ? W.rank : nullptr;
-    P.fault = c->d_fault_rec;
     P.n = n;
     P.stride = win_stride;
     P.chunk = lay.chunk;
@@ -4367,8 +4496,6 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     P.ncol = lay.ncol;
     P.ct_shift = lay.ct_shift;
     P.filter = b->filter;
-    P.kni_bm = c->d_kni;
-    P.kni_enable = c->kni_enable ? 1u : 0u;
     P.rank_pack = ranked && lp.packed ? 1u : 0u;
     const uint32_t tset = W.tot_set;
     P.tot_acc = fused ? W.tot_acc + (size_t)tset * c->nb : nullptr;
@@ -4522,43 +4649,22 @@ static int dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, bool route,
     const uint32_t nbk = route ? c->nb + 2u : c->nb;
     if (nbk > YRSS_SEG_MAX_BUCKETS)
         return -ENOTSUP;
-    if (b->win_stride < YRSS_WIN_MIN || (b->win_stride & 15u) || n > YRSS_SEG_MAX_BATCH)
-        return -EINVAL;
-    if (n && (!b->win || !b->len || !b->q || !b->seg_idx || !b->seg_off))
-        return -EINVAL;
-    if (((uintptr_t)b->win & 15u) || ((uintptr_t)b->len & 1u) || ((uintptr_t)b->q & 1u) ||
-        ((uintptr_t)b->hash & 3u) || ((uintptr_t)b->seg_idx & 15u) ||
-        ((uintptr_t)b->seg_off & 1u))
-        return -EINVAL;
-    if (n == 0)
-        return 0;
+    int rc = check_dev_batch(b->win, b->win_stride, b->len, n, YRSS_SEG_MAX_BATCH, b->q, b->hash,
+                             {b->seg_idx, 15u}, {b->seg_off, 1u}, true);
+    if (rc || n == 0)
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (c->w.running) {      // the resident worker holds CUs the grid needs
-        const int rc = worker_halt(c);
-        if (rc)
-            return rc;
-    }
-    if (c->last_stream_valid && c->last_stream != s) {
-        YRSS_HIP(hipEventRecord(c->switch_ev, c->last_stream));
-        YRSS_HIP(hipStreamWaitEvent(s, c->switch_ev, 0));
-    }
-    c->last_stream = s;
-    c->last_stream_valid = true;
+    if ((rc = take_stream(c, s)) != 0)
+        return rc;
     // (the route classes need the filter class whether or not it is stored)
     const bool filter = route || b->filter != nullptr;
-    ParseParams P = c->proto;
+    ParseParams P = parse_params(c, route ? (int)queue_id : -1, true);   // (nb = nbk)
     P.win = b->win;
     P.len = b->len;
     P.q = b->q;
     P.hash = b->hash;
-    P.seg_cnt = nullptr;
-    P.rank = nullptr;
-    P.fault = c->d_fault_rec;
     P.n = n;
     P.stride = b->win_stride;
-    P.nb = nbk;
-    P.route_lq = queue_id;
-    P.route_accept = c->kni_accept ? 1 : 0;
     // a chunk is a segment: 4 tiles, the parse kernel's output burst
     // (yrss_tuning.chunk_tiles does not apply)
     static_assert(YRSS_SEG_PKTS == kOutTiles * kTile, "a segment is one output burst");
@@ -4568,14 +4674,7 @@ static int dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, bool route,
     P.chunk = YRSS_SEG_PKTS;
     P.ct_shift = 2;
     P.nchunk = (n + YRSS_SEG_PKTS - 1u) / YRSS_SEG_PKTS;
-    P.ncol = 0;
     P.filter = b->filter;
-    P.kni_bm = c->d_kni;
-    P.kni_enable = c->kni_enable ? 1u : 0u;
-    P.rank_pack = 0;
-    P.tot_acc = nullptr;
-    P.rbin = nullptr;
-    P.rbin_chunks = 0;
     P.seg_idx = b->seg_idx;
     P.seg_off = b->seg_off;
     {
@@ -4608,38 +4707,21 @@ int yrss_dispatch_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t
     if (!c || (n && (!data || !len || !out_q)))
         return -EINVAL;
     if (n == 0) {
-        if (out_qstart)
-            memset(out_qstart, 0, (c->nb + 1) * sizeof(uint32_t));
+        zero_offsets(out_qstart, c->nb);
         return 0;
     }
-    int rc = begin_burst(c);
-    if (rc)
-        return rc;
-    YRSS_HIP(hipSetDevice(c->device));
-    uint32_t W = 0;
-    if ((rc = gather_frames(c, data, len, n, &W)) != 0)
-        return rc;
-    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_qidx, out_qstart, nullptr,
-                              false)) != 0)
-        return rc;
-    return finish_burst(c);
+    return staged_burst(c, data, len, n, out_q, out_hash, out_qidx, out_qstart, nullptr, -1, 0);
 }
 
 int yrss_route_lists_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len,
                             uint32_t n, uint16_t queue_id, int16_t *out_q, uint32_t *out_hash,
                             int8_t *out_filter, uint32_t *out_ridx, uint32_t *out_rstart)
 {
-    int rc = route_lists_begin(c, n, data, len, out_q, out_ridx, out_rstart);
+    const int rc = route_lists_begin(c, n, data, len, out_q, out_ridx, out_rstart);
     if (rc)
         return rc < 0 ? rc : 0;
-    YRSS_HIP(hipSetDevice(c->device));
-    uint32_t W = 0;
-    if ((rc = gather_frames(c, data, len, n, &W)) != 0)
-        return rc;
-    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_ridx, out_rstart, out_filter, false,
-                              (int)queue_id)) != 0)
-        return rc;
-    return finish_burst(c);
+    return staged_burst(c, data, len, n, out_q, out_hash, out_ridx, out_rstart, out_filter,
+                        (int)queue_id, 0);
 }
 
 int yrss_set_dispatch_ctx(yrss_ctx *c)
@@ -4732,23 +4814,11 @@ int yrss_dispatch_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, int16_t *ou
     if (!c || (n && (!mbufs || !out_q)))
         return -EINVAL;
     if (n == 0) {
-        if (out_qstart)
-            memset(out_qstart, 0, (c->nb + 1) * sizeof(uint32_t));
+        zero_offsets(out_qstart, c->nb);
         return 0;
     }
-    int rc = begin_burst(c);
-    if (rc)
-        return rc;
-    YRSS_HIP(hipSetDevice(c->device));
-    uint32_t W = 0;
-    if ((rc = gather_mbufs(c, mbufs, n, &W)) != 0)
-        return rc;
-    const bool wb = (flags & YRSS_F_WRITE_RSS) != 0;
-    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_qidx, out_qstart, nullptr, wb)) != 0)
-        return rc;
-    if (wb)
-        c->pend.wb_mbufs = mbufs;
-    return end_burst(c, flags);
+    return staged_burst(c, mbufs, nullptr, n, out_q, out_hash, out_qidx, out_qstart, nullptr, -1,
+                        flags);
 }
 
 int yrss_route_lists_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, uint16_t queue_id,
@@ -4757,20 +4827,11 @@ int yrss_route_lists_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, uint16_t
 {
     if (flags & ~YRSS_F_WRITE_RSS)
         return -EINVAL;
-    int rc = route_lists_begin(c, n, mbufs, mbufs, out_q, out_ridx, out_rstart);
+    const int rc = route_lists_begin(c, n, mbufs, mbufs, out_q, out_ridx, out_rstart);
     if (rc)
         return rc < 0 ? rc : 0;
-    YRSS_HIP(hipSetDevice(c->device));
-    uint32_t W = 0;
-    if ((rc = gather_mbufs(c, mbufs, n, &W)) != 0)
-        return rc;
-    const bool wb = (flags & YRSS_F_WRITE_RSS) != 0;
-    if ((rc = classify_staged(c, n, W, out_q, out_hash, out_ridx, out_rstart, out_filter, wb,
-                              (int)queue_id)) != 0)
-        return rc;
-    if (wb)
-        c->pend.wb_mbufs = mbufs;
-    return finish_burst(c);
+    return staged_burst(c, mbufs, nullptr, n, out_q, out_hash, out_ridx, out_rstart, out_filter,
+                        (int)queue_id, flags);
 }
 
 int yrss_register_host_memory(yrss_ctx *c, void *base, size_t len)
@@ -4822,17 +4883,6 @@ int yrss_unregister_host_memory(yrss_ctx *c, void *base)
 
 namespace {
 
-// Device-visible alias of host bytes [p, p+bytes) if they lie in a registered
-// range, else nullptr.
-const void *dev_alias(const yrss_ctx *c, const void *p, size_t bytes)
-{
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    for (uint32_t r = 0; r < c->nranges; ++r)
-        if (a >= c->ranges[r].lo && a + bytes <= c->ranges[r].hi)
-            return (const void *)(uintptr_t)(a + c->ranges[r].delta);
-    return nullptr;
-}
-
 int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n, bool frames,
                 int16_t *out_q, uint32_t *out_hash, uint32_t *out_qidx, uint32_t *out_qstart,
                 uint32_t flags)
@@ -4843,8 +4893,7 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
                     ml.off_data_len + 2u > 64u || ml.off_hash_rss % 4u))
         return -EINVAL;                      // header fields must sit in the first 64 bytes
     if (n == 0) {
-        if (out_qstart)
-            memset(out_qstart, 0, (c->nb + 1) * sizeof(uint32_t));
+        zero_offsets(out_qstart, c->nb);
         return 0;
     }
     int rc = begin_burst(c);
@@ -4857,6 +4906,7 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
     const bool small = small_ok(c, n);
     GatherParams G;
     memset(&G, 0, sizeof(G));
+    gather_config(c, G);
     // The pointer (and length) arrays are read in place when registered; else
     // from the pinned staging, in place too on the small-burst path.
     G.ptrs = (const uint64_t *)dev_alias(c, ptrs, (size_t)n * 8);
@@ -4888,21 +4938,9 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
     G.hash = c->d_hash;
     G.n = n;
     G.frames = frames ? 1u : 0u;
-    G.nranges = c->nranges;
-    G.off_buf_addr = ml.off_buf_addr;
-    G.off_data_off = ml.off_data_off;
-    G.off_data_len = ml.off_data_len;
-    G.off_hash_rss = ml.off_hash_rss;
-    memcpy(G.ranges, c->ranges, sizeof(G.ranges));
-    const bool compact = out_qidx && out_qstart;
     const bool want_hash = out_hash || (flags & YRSS_F_WRITE_RSS);
-    PendingBurst &p = c->pend;
-    p = PendingBurst{};
-    p.n = n;
-    p.outs[0] = {out_q, c->h_q, (size_t)n * 2, false};
-    p.outs[1] = {out_hash, c->h_hash, (size_t)n * 4, false};
-    p.outs[2] = {compact ? out_qidx : nullptr, c->h_qidx, (size_t)n * 4, false};
-    p.outs[3] = {compact ? out_qstart : nullptr, c->h_qstart, (c->nb + 1) * 4, false};
+    PendingBurst &p = pend_setup(c, n, out_q, out_hash, out_qidx, out_qstart, nullptr,
+                                 c->nb + 1u);
     p.gather_fault = true;
     for (int k = 0; k < 4; ++k)
         p.outs[k].direct = p.outs[k].user && dev_alias(c, p.outs[k].user, p.outs[k].bytes);
@@ -4911,8 +4949,7 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
         // (the caller's arrays when registered, else the pinned staging)
         *c->h_fault = 0;
         G.fault = c->dh_fault;
-        SmallParams S;
-        memset(&S, 0, sizeof(S));
+        SmallParams S = small_params(c);
         S.G = G;
         S.gather = 1;
         S.writeback = (!frames && (flags & YRSS_F_WRITE_RSS)) ? 1u : 0u;
@@ -4941,33 +4978,14 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
     const uint32_t blocks = std::min<uint32_t>((n + 63u) / 64u, (uint32_t)c->cus * 8u);
     hipLaunchKernelGGL(yrss_gather_zc, dim3(blocks), dim3(256), 0, s, G);
     YRSS_HIP(hipGetLastError());
-    yrss_dev_batch b;
-    b.win = c->d_win;
-    b.win_stride = YRSS_WIN_FULL;
-    b.n = n;
-    b.len = c->d_len;
-    b.q = c->d_q;
-    b.hash = want_hash ? c->d_hash : nullptr;
-    b.qidx = compact ? c->d_qidx : nullptr;
-    b.qstart = compact ? c->d_qstart : nullptr;
-    b.filter = nullptr;
-    if ((rc = dispatch_dev_impl(c, &b, s)) != 0)
+    if ((rc = staged_dev_batch(c, YRSS_WIN_FULL, want_hash)) != 0)
         return rc;
     if (!frames && (flags & YRSS_F_WRITE_RSS)) {
         hipLaunchKernelGGL(yrss_writeback_zc, dim3((n + 255u) / 256u), dim3(256), 0, s, G);
         YRSS_HIP(hipGetLastError());
     }
-    const void *src[4] = {c->d_q, c->d_hash, c->d_qidx, c->d_qstart};
     YRSS_HIP(hipMemcpyAsync(c->h_fault, c->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    for (int k = 0; k < 4; ++k) {
-        if (!p.outs[k].user)
-            continue;
-        YRSS_HIP(hipMemcpyAsync(p.outs[k].direct ? p.outs[k].user : p.outs[k].stage, src[k],
-                                p.outs[k].bytes, hipMemcpyDeviceToHost, s));
-    }
-    p.dev_fault = compact;
-    p.active = true;
-    return 0;
+    return staged_copy_back(c, false);   // (the write-back ran on the device)
 }
 
 }  // namespace
@@ -5019,22 +5037,13 @@ int yrss_route_burst(yrss_ctx *c, void *const *mbufs, uint32_t n, uint16_t queue
     memset(res, 0, sizeof(*res));
     if (n == 0)
         return 0;
-    int rc = begin_burst(c);
-    if (rc)
-        return rc;
-    YRSS_HIP(hipSetDevice(c->device));
-    uint32_t W = 0;
-    if ((rc = gather_mbufs(c, mbufs, n, &W)) != 0)
-        return rc;
     std::vector<int16_t> q(n);
     std::vector<int8_t> fc(n);
     // (the per-queue lists are not read here; asking for them keeps the launch
     // what it has always been)
     std::vector<uint32_t> qidx(n), qstart(c->nb + 1);
-    rc = classify_staged(c, n, W, q.data(), nullptr, qidx.data(), qstart.data(), fc.data(),
-                         false);
-    if (rc == 0)
-        rc = finish_burst(c);
+    const int rc = staged_burst(c, mbufs, nullptr, n, q.data(), nullptr, qidx.data(),
+                                qstart.data(), fc.data(), -1, 0);
     if (rc)
         return rc;
     // the hand-off itself: the one routine of yrss_route_seg / yrss_route_lists,
@@ -5165,25 +5174,14 @@ int worker_launch(yrss_ctx *c)
     auto &w = c->w;
     WorkerParams W;
     memset(&W, 0, sizeof(W));
-    W.P = c->proto;
+    // a route worker (nb = w.nbk) has the KNI state as the context holds it
+    // now: yrss_set_kni halts it, so a launch never outlives the state it was
+    // given; a plain worker stores no filter class and has none
+    W.P = parse_params(c, w.route ? (int)w.route_lq : -1, false);
     W.P.fault = nullptr;   // per burst: W.brec, then the slot's srec entry
-    W.P.kni_bm = c->d_kni;
-    W.P.kni_enable = 0;
-    if (w.route) {
-        // the KNI state as the context holds it now: yrss_set_kni halts a
-        // route worker, so a launch never outlives the state it was given
-        W.P.nb = w.nbk;
-        W.P.kni_enable = c->kni_enable ? 1u : 0u;
-        W.P.route_lq = w.route_lq;
-        W.P.route_accept = c->kni_accept ? 1 : 0;
-    }
-    const yrss_mbuf_layout &ml = c->cfg.mbuf;
-    W.G.nranges = c->nranges;
-    W.G.off_buf_addr = ml.off_buf_addr;
-    W.G.off_data_off = ml.off_data_off;
-    W.G.off_data_len = ml.off_data_len;
-    W.G.off_hash_rss = ml.off_hash_rss;
-    memcpy(W.G.ranges, c->ranges, sizeof(W.G.ranges));
+    if (!w.route)
+        W.P.kni_enable = 0;
+    gather_config(c, W.G);
     W.slots = w.d_slots;
     W.done = w.d_done;
     W.fault = w.fault;
@@ -5360,10 +5358,7 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     for (int k = 0; k < 4; ++k) {
         uint64_t d = 0;
         if (user[k]) {
-            const uint64_t u = (uint64_t)(uintptr_t)user[k];
-            for (uint32_t r = 0; r < c->nranges && !d; ++r)
-                if (u >= c->ranges[r].lo && u + bytes[k] <= c->ranges[r].hi)
-                    d = u + (uint64_t)c->ranges[r].delta;
+            d = (uint64_t)(uintptr_t)dev_alias(c, user[k], bytes[k]);
             if (!d) {
                 d = (uint64_t)(uintptr_t)stage[k];
                 copy |= (uint8_t)(1u << k);

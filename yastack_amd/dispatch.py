@@ -78,9 +78,12 @@ class SegResult:
         return self.seg_idx[base + int(o[b]):base + int(o[b + 1])]
 
 
-def _check_dev_sizes(n, stride, win, lens, out, nb_queues):
+def _check_sizes(n, stride, win, lens, out, required=(), optional=()):
     """The C ABI takes raw device pointers and cannot see the buffers' sizes: a
-    batch larger than its buffers would fault the GPU.  Refuse it here."""
+    batch larger than its buffers would fault the GPU.  Refuse it here.  Beside
+    win, lens, q and the optional hash and filter a form has rows of its own,
+    (name, buffer, bytes): ``required`` ones, and ``optional`` ones that are
+    checked where the buffer is given."""
     def nbytes(t):
         return 0 if t is None else int(t.numel()) * int(t.element_size())
     if n < 0:
@@ -88,41 +91,27 @@ def _check_dev_sizes(n, stride, win, lens, out, nb_queues):
     if n == 0:
         return
     # the kernel may read any byte below the stride of a window (rare header walks)
-    need = [("win", win, n * stride), ("lens", lens, 2 * n),
-            ("q", out.q, 2 * n)]
-    if out.hash is not None:
-        need.append(("hash", out.hash, 4 * n))
-    if out.qidx is not None:
-        need.append(("qidx", out.qidx, 4 * n))
-    if out.qstart is not None:
-        need.append(("qstart", out.qstart, 4 * (nb_queues + 2)))
-    if out.filter is not None:
-        need.append(("filter", out.filter, n))
+    need = [("win", win, n * stride), ("lens", lens, 2 * n), ("q", out.q, 2 * n), *required]
+    need += [row for row in (("hash", out.hash, 4 * n), *optional, ("filter", out.filter, n))
+             if row[1] is not None]
     for name, t, b in need:
         if nbytes(t) < b:
             raise ValueError(f"{name} holds {nbytes(t)} bytes, the batch of {n} needs {b}")
+
+
+def _check_dev_sizes(n, stride, win, lens, out, nb_queues):
+    """_check_sizes for the global lists' buffers."""
+    _check_sizes(n, stride, win, lens, out, optional=(
+        ("qidx", out.qidx, 4 * n), ("qstart", out.qstart, 4 * (nb_queues + 2))))
 
 
 def _check_seg_sizes(n, stride, win, lens, out, nb_queues, nbk=None):
-    """As _check_dev_sizes, for the segmented form's buffers (nbk buckets a
-    segment: nb_queues + 1, or the routed form's nb_queues + 3)."""
+    """_check_sizes for the segmented form's buffers (nbk buckets a segment:
+    nb_queues + 1, or the routed form's nb_queues + 3)."""
     nbk = nb_queues + 1 if nbk is None else nbk
-    def nbytes(t):
-        return 0 if t is None else int(t.numel()) * int(t.element_size())
-    if n < 0:
-        raise ValueError("negative batch size")
-    if n == 0:
-        return
     nseg = -(-n // abi.SEG_PKTS)
-    need = [("win", win, n * stride), ("lens", lens, 2 * n), ("q", out.q, 2 * n),
-            ("seg_idx", out.seg_idx, n), ("seg_off", out.seg_off, 2 * nseg * (nbk + 1))]
-    if out.hash is not None:
-        need.append(("hash", out.hash, 4 * n))
-    if out.filter is not None:
-        need.append(("filter", out.filter, n))
-    for name, t, b in need:
-        if nbytes(t) < b:
-            raise ValueError(f"{name} holds {nbytes(t)} bytes, the batch of {n} needs {b}")
+    _check_sizes(n, stride, win, lens, out, required=(
+        ("seg_idx", out.seg_idx, n), ("seg_off", out.seg_off, 2 * nseg * (nbk + 1))))
 
 
 def _ptr(t) -> int | None:
@@ -131,6 +120,43 @@ def _ptr(t) -> int | None:
     if isinstance(t, np.ndarray):
         return t.ctypes.data
     return t.data_ptr()
+
+
+def _host_out(n, noff, want_hash=True, compact=True, want_filter=False):
+    """The host output arrays of one burst, (q, hash, qidx, qstart, filter): n
+    entries each (one at least) and noff offsets, None where not wanted.  The
+    routed forms always have their lists (compact) and may have the filter."""
+    m = max(n, 1)
+    return (np.empty(m, np.int16),
+            np.empty(m, np.uint32) if want_hash else None,
+            np.empty(m, np.uint32) if compact else None,
+            np.empty(noff, np.uint32) if compact else None,
+            np.empty(m, np.int8) if want_filter else None)
+
+
+def _host_result(n, out) -> DispatchResult:
+    """_host_out's arrays, the per-packet ones cut to the burst's n."""
+    q, h, qi, _, f = (None if a is None else a[:n] for a in out)
+    return DispatchResult(q, h, qi, out[3], f)   # (the offsets are whole)
+
+
+def _frame_ptrs(frames):
+    """A list of frames (bytes) as the C calls take it: (the data pointers, the
+    lengths, the buffers the pointers point into, to be kept until the call
+    has returned)."""
+    sizes = [len(f) for f in frames]
+    if any(size > 65535 for size in sizes):
+        raise ValueError("frame longer than 65535 bytes")
+    bufs = [np.frombuffer(bytes(f), dtype=np.uint8) if len(f) else np.zeros(1, np.uint8)
+            for f in frames]
+    ptrs = np.array([b.ctypes.data for b in bufs], dtype=np.uint64)
+    return ptrs, np.array(sizes, dtype=np.uint16), bufs
+
+
+def _flat(a, dtype):
+    """A host array as the flat contiguous one of dtype that a C hand-off
+    reads (None stays None)."""
+    return None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1)).view(dtype)
 
 
 class SoftRss:
@@ -261,13 +287,16 @@ class SoftRss:
         return out
 
     def alloc_seg_out(self, n: int, dev, want_hash=True, want_filter=False) -> SegResult:
+        return self._alloc_seg(n, dev, want_hash, want_filter, self.nb_queues + 2)
+
+    def _alloc_seg(self, n, dev, want_hash, want_filter, noff) -> SegResult:
         torch = self._torch()
         nseg = max(-(-n // abi.SEG_PKTS), 1)
         q = torch.empty(max(n, 1), dtype=torch.int16, device=dev)
         h = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if want_hash else None
         f = torch.empty(max(n, 1), dtype=torch.int8, device=dev) if want_filter else None
         si = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        so = torch.empty((nseg, self.nb_queues + 2), dtype=torch.int16, device=dev)
+        so = torch.empty((nseg, noff), dtype=torch.int16, device=dev)
         return SegResult(q, h, f, si, so, n)
 
     def route_dev_seg(self, win, lens, stride: int, queue_id: int, n: int | None = None, *,
@@ -292,11 +321,7 @@ class SoftRss:
     def alloc_route_out(self, n: int, dev, want_hash=True, want_filter=False) -> SegResult:
         """Output buffers of :meth:`route_dev_seg`: those of the segmented form
         with nb_queues + 4 offsets a segment."""
-        torch = self._torch()
-        out = self.alloc_seg_out(n, dev, want_hash, want_filter)
-        nseg = max(-(-n // abi.SEG_PKTS), 1)
-        out.seg_off = torch.empty((nseg, self.nb_queues + 4), dtype=torch.int16, device=dev)
-        return out
+        return self._alloc_seg(n, dev, want_hash, want_filter, self.nb_queues + 4)
 
     def alloc_out(self, n: int, dev, want_hash=True, compact=True,
                   want_filter=False) -> DispatchResult:
@@ -325,21 +350,12 @@ class SoftRss:
     def dispatch_frames(self, frames, want_hash=True, compact=True) -> DispatchResult:
         """Classify a list of frames (bytes) — one toeplitz_dispatch per frame."""
         n = len(frames)
-        bufs = [np.frombuffer(bytes(f), dtype=np.uint8) if len(f) else np.zeros(1, np.uint8)
-                for f in frames]
-        ptrs = np.array([b.ctypes.data for b in bufs], dtype=np.uint64)
-        lens = np.array([len(f) for f in frames], dtype=np.uint16)
-        if np.any(lens != np.array([len(f) for f in frames])):
-            raise ValueError("frame longer than 65535 bytes")
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32) if want_hash else None
-        qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self.nb_queues + 2, np.uint32) if compact else None
-        rc = self._lib.yrss_dispatch_frames(self._ctx, _ptr(ptrs), _ptr(lens), n, _ptr(q),
-                                            _ptr(h), _ptr(qi), _ptr(qs))
+        ptrs, lens, _bufs = _frame_ptrs(frames)
+        out = _host_out(n, self.nb_queues + 2, want_hash, compact)
+        rc = self._lib.yrss_dispatch_frames(self._ctx, _ptr(ptrs), _ptr(lens), n,
+                                            *map(_ptr, out[:4]))
         abi.check(rc, "yrss_dispatch_frames")
-        return DispatchResult(q[:n], None if h is None else h[:n],
-                              None if qi is None else qi[:n], qs)
+        return _host_result(n, out)
 
     def dispatch_burst(self, mbuf_ptrs: np.ndarray, want_hash=True, compact=True,
                        write_rss=False, async_=False) -> DispatchResult:
@@ -347,19 +363,19 @@ class SoftRss:
 
         ``async_=True`` (YRSS_F_ASYNC) returns once the burst is queued; the
         result's arrays are valid after :meth:`wait`."""
+        return self._burst("yrss_dispatch_burst", mbuf_ptrs, want_hash, compact, write_rss,
+                           async_)
+
+    def _burst(self, name, mbuf_ptrs, want_hash, compact, write_rss, async_) -> DispatchResult:
+        """dispatch_burst / dispatch_burst_zc: the C call ``name`` on the burst."""
         mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
         n = int(mb.size)
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32) if want_hash else None
-        qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self.nb_queues + 2, np.uint32) if compact else None
+        out = _host_out(n, self.nb_queues + 2, want_hash, compact)
         flags = (abi.F_WRITE_RSS if write_rss else 0) | (abi.F_ASYNC if async_ else 0)
-        rc = self._lib.yrss_dispatch_burst(self._ctx, _ptr(mb), n, _ptr(q), _ptr(h), _ptr(qi),
-                                           _ptr(qs), flags)
-        abi.check(rc, "yrss_dispatch_burst")
+        rc = getattr(self._lib, name)(self._ctx, _ptr(mb), n, *map(_ptr, out[:4]), flags)
+        abi.check(rc, name)
         self._inflight = mb if async_ else None   # keep the pointer array alive
-        return DispatchResult(q[:n], None if h is None else h[:n],
-                              None if qi is None else qi[:n], qs)
+        return _host_result(n, out)
 
     def wait(self) -> None:
         """Complete the burst queued with ``async_=True`` (``yrss_wait``)."""
@@ -392,17 +408,19 @@ class SoftRss:
         its ticket.  :meth:`worker_poll` returns the DispatchResult."""
         mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
         n = int(mb.size)
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32) if want_hash else None
-        qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self._wk_offsets, np.uint32) if compact else None
+        flags = abi.F_WRITE_RSS if write_rss else 0
+        return self._worker_queue(
+            "yrss_worker_submit", n, want_hash, compact,
+            lambda outs, t: self._lib.yrss_worker_submit(self._ctx, _ptr(mb), n, *outs, flags, t))
+
+    def _worker_queue(self, name, n, want_hash, compact, call) -> int:
+        """The three worker submits: ``call(outs, ticket)`` makes the C call
+        ``name`` with the burst's four output pointers and the ticket to fill;
+        the DispatchResult waits under its ticket for :meth:`worker_poll`."""
+        out = _host_out(n, self._wk_offsets, want_hash, compact)
         t = ctypes.c_uint64()
-        rc = self._lib.yrss_worker_submit(self._ctx, _ptr(mb), n, _ptr(q), _ptr(h), _ptr(qi),
-                                          _ptr(qs), abi.F_WRITE_RSS if write_rss else 0,
-                                          ctypes.byref(t))
-        abi.check(rc, "yrss_worker_submit")
-        self._wk[t.value] = DispatchResult(q[:n], None if h is None else h[:n],
-                                           None if qi is None else qi[:n], qs)
+        abi.check(call([_ptr(a) for a in out[:4]], ctypes.byref(t)), name)
+        self._wk[t.value] = _host_result(n, out)
         return t.value
 
     def worker_submit_frames(self, data_ptrs: np.ndarray, lens: np.ndarray, want_hash=True,
@@ -414,17 +432,10 @@ class SoftRss:
         n = int(dp.size)
         if ln.size != n:
             raise ValueError("data_ptrs and lens differ in length")
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32) if want_hash else None
-        qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self._wk_offsets, np.uint32) if compact else None
-        t = ctypes.c_uint64()
-        rc = self._lib.yrss_worker_submit_frames(self._ctx, _ptr(dp), _ptr(ln), n, _ptr(q),
-                                                 _ptr(h), _ptr(qi), _ptr(qs), ctypes.byref(t))
-        abi.check(rc, "yrss_worker_submit_frames")
-        self._wk[t.value] = DispatchResult(q[:n], None if h is None else h[:n],
-                                           None if qi is None else qi[:n], qs)
-        return t.value
+        return self._worker_queue(
+            "yrss_worker_submit_frames", n, want_hash, compact,
+            lambda outs, t: self._lib.yrss_worker_submit_frames(self._ctx, _ptr(dp), _ptr(ln), n,
+                                                                *outs, t))
 
     def worker_submit_windows(self, win: np.ndarray, stride: int, lens: np.ndarray,
                               want_hash=True, compact=True) -> int:
@@ -432,18 +443,10 @@ class SoftRss:
         that lie in registered memory (``yrss_worker_submit_windows``)."""
         ln = np.ascontiguousarray(lens, dtype=np.uint16)
         n = int(ln.size)
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32) if want_hash else None
-        qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self._wk_offsets, np.uint32) if compact else None
-        t = ctypes.c_uint64()
-        rc = self._lib.yrss_worker_submit_windows(self._ctx, _ptr(win), stride, _ptr(ln), n,
-                                                  _ptr(q), _ptr(h), _ptr(qi), _ptr(qs),
-                                                  ctypes.byref(t))
-        abi.check(rc, "yrss_worker_submit_windows")
-        self._wk[t.value] = DispatchResult(q[:n], None if h is None else h[:n],
-                                           None if qi is None else qi[:n], qs)
-        return t.value
+        return self._worker_queue(
+            "yrss_worker_submit_windows", n, want_hash, compact,
+            lambda outs, t: self._lib.yrss_worker_submit_windows(self._ctx, _ptr(win), stride,
+                                                                 _ptr(ln), n, *outs, t))
 
     def toeplitz_dispatch(self, frame: bytes, queue_id: int = 0) -> int:
         """The per-packet registration shim (``yrss_toeplitz_dispatch``) on this
@@ -479,19 +482,8 @@ class SoftRss:
                           write_rss=False, async_=False) -> DispatchResult:
         """Zero-copy burst: mbufs in registered host memory are read by the GPU.
         ``async_`` as in :meth:`dispatch_burst`."""
-        mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
-        n = int(mb.size)
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32) if want_hash else None
-        qi = np.empty(max(n, 1), np.uint32) if compact else None
-        qs = np.empty(self.nb_queues + 2, np.uint32) if compact else None
-        flags = (abi.F_WRITE_RSS if write_rss else 0) | (abi.F_ASYNC if async_ else 0)
-        rc = self._lib.yrss_dispatch_burst_zc(self._ctx, _ptr(mb), n, _ptr(q), _ptr(h), _ptr(qi),
-                                              _ptr(qs), flags)
-        abi.check(rc, "yrss_dispatch_burst_zc")
-        self._inflight = mb if async_ else None
-        return DispatchResult(q[:n], None if h is None else h[:n],
-                              None if qi is None else qi[:n], qs)
+        return self._burst("yrss_dispatch_burst_zc", mbuf_ptrs, want_hash, compact, write_rss,
+                           async_)
 
     def route_burst(self, mbuf_ptrs: np.ndarray, queue_id: int, enqueue, clone, release,
                     kni_primary: bool = True):
@@ -529,12 +521,6 @@ class SoftRss:
         abi.check(call(ctypes.byref(ops), _ptr(local), _ptr(kni), ctypes.byref(res)), name)
         return local[:res.n_local].tolist(), kni[:res.n_kni].tolist(), res
 
-    def _route_lists_out(self, n, want_hash, want_filter):
-        return (np.empty(max(n, 1), np.int16),
-                np.empty(max(n, 1), np.uint32) if want_hash else None,
-                np.empty(max(n, 1), np.int8) if want_filter else None,
-                np.empty(max(n, 1), np.uint32), np.empty(self.nb_queues + 4, np.uint32))
-
     def route_lists_frames(self, frames, queue_id: int, want_hash=True,
                            want_filter=True) -> DispatchResult:
         """Classify a list of frames (bytes) into process_packets' hand-off
@@ -543,18 +529,13 @@ class SoftRss:
         result's ``qidx`` / ``qstart`` are the routed lists: packet indices
         grouped by route class and nb_queues + 4 offsets."""
         n = len(frames)
-        bufs = [np.frombuffer(bytes(f), dtype=np.uint8) if len(f) else np.zeros(1, np.uint8)
-                for f in frames]
-        ptrs = np.array([b.ctypes.data for b in bufs], dtype=np.uint64)
-        lens = np.array([len(f) for f in frames], dtype=np.uint16)
-        if np.any(lens != np.array([len(f) for f in frames])):
-            raise ValueError("frame longer than 65535 bytes")
-        q, h, f, ri, rs = self._route_lists_out(n, want_hash, want_filter)
+        ptrs, lens, _bufs = _frame_ptrs(frames)
+        out = _host_out(n, self.nb_queues + 4, want_hash, want_filter=want_filter)
+        q, h, ri, rs, f = map(_ptr, out)
         rc = self._lib.yrss_route_lists_frames(self._ctx, _ptr(ptrs), _ptr(lens), n, queue_id,
-                                               _ptr(q), _ptr(h), _ptr(f), _ptr(ri), _ptr(rs))
+                                               q, h, f, ri, rs)
         self._ck(rc, "yrss_route_lists_frames")
-        return DispatchResult(q[:n], None if h is None else h[:n], ri[:n], rs,
-                              None if f is None else f[:n])
+        return _host_result(n, out)
 
     def route_lists_burst(self, mbuf_ptrs: np.ndarray, queue_id: int, want_hash=True,
                           want_filter=True, write_rss=False) -> DispatchResult:
@@ -562,13 +543,12 @@ class SoftRss:
         ``yrss_route_lists_burst``)."""
         mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
         n = int(mb.size)
-        q, h, f, ri, rs = self._route_lists_out(n, want_hash, want_filter)
-        rc = self._lib.yrss_route_lists_burst(self._ctx, _ptr(mb), n, queue_id, _ptr(q), _ptr(h),
-                                              _ptr(f), _ptr(ri), _ptr(rs),
+        out = _host_out(n, self.nb_queues + 4, want_hash, want_filter=want_filter)
+        q, h, ri, rs, f = map(_ptr, out)
+        rc = self._lib.yrss_route_lists_burst(self._ctx, _ptr(mb), n, queue_id, q, h, f, ri, rs,
                                               abi.F_WRITE_RSS if write_rss else 0)
         self._ck(rc, "yrss_route_lists_burst")
-        return DispatchResult(q[:n], None if h is None else h[:n], ri[:n], rs,
-                              None if f is None else f[:n])
+        return _host_result(n, out)
 
     def route_lists(self, result_or_arrays, objs, queue_id: int, enqueue, clone, release,
                     kni_primary: bool = True):
@@ -585,12 +565,9 @@ class SoftRss:
         else:
             ridx, rstart, *rest = result_or_arrays
             filt = rest[0] if rest else None
-        ridx = np.ascontiguousarray(np.asarray(ridx).reshape(-1)).view(np.uint32)
-        rstart = np.ascontiguousarray(np.asarray(rstart).reshape(-1)).view(np.uint32)
+        ridx, rstart, filt = _flat(ridx, np.uint32), _flat(rstart, np.uint32), _flat(filt, np.int8)
         mb = np.ascontiguousarray(objs, dtype=np.uint64)
         n = int(mb.size)
-        if filt is not None:
-            filt = np.ascontiguousarray(np.asarray(filt).reshape(-1)).view(np.int8)
         # the C call sees raw pointers only: the sizes are checked here
         if ridx.size < n or rstart.size < self.nb_queues + 4 or \
                 (filt is not None and filt.size < n):
@@ -621,11 +598,9 @@ class SoftRss:
             filt = rest[0] if rest else None
             n = int(n)
         nseg = -(-n // abi.SEG_PKTS)
-        seg_idx = np.ascontiguousarray(np.asarray(seg_idx).reshape(-1)).view(np.uint8)
-        seg_off = np.ascontiguousarray(np.asarray(seg_off).reshape(-1)).view(np.uint16)
+        seg_idx, seg_off, filt = (_flat(seg_idx, np.uint8), _flat(seg_off, np.uint16),
+                                  _flat(filt, np.int8))
         mb = np.ascontiguousarray(objs, dtype=np.uint64)
-        if filt is not None:
-            filt = np.ascontiguousarray(np.asarray(filt).reshape(-1)).view(np.int8)
         # the C call sees raw pointers only: the sizes are checked here
         if seg_idx.size < n or seg_off.size < nseg * (self.nb_queues + 4) or mb.size < n or \
                 (filt is not None and filt.size < n):
@@ -745,35 +720,28 @@ class FanOut:
         abi.check(self._lib.yrss_fanout_unregister_host_memory(self._f, base),
                   "yrss_fanout_unregister_host_memory")
 
-    def _outs(self, n):
-        q = np.empty(max(n, 1), np.int16)
-        h = np.empty(max(n, 1), np.uint32)
-        qi = np.empty(max(n, 1), np.uint32)
-        qs = np.empty(self.nb_queues + 2, np.uint32)
-        return q, h, qi, qs
+    def _queue(self, name, n, call) -> int:
+        """As SoftRss._worker_queue: ``call(outs, ticket)`` makes the C call ``name``."""
+        out = _host_out(n, self.nb_queues + 2)
+        t = ctypes.c_uint64()
+        abi.check(call([_ptr(a) for a in out[:4]], ctypes.byref(t)), name)
+        self._res[t.value] = _host_result(n, out)
+        return t.value
 
     def submit(self, mbuf_ptrs: np.ndarray) -> int:
         mb = np.ascontiguousarray(mbuf_ptrs, dtype=np.uint64)
         n = int(mb.size)
-        q, h, qi, qs = self._outs(n)
-        t = ctypes.c_uint64()
-        abi.check(self._lib.yrss_fanout_submit(self._f, _ptr(mb), n, _ptr(q), _ptr(h), _ptr(qi),
-                                               _ptr(qs), 0, ctypes.byref(t)), "yrss_fanout_submit")
-        self._res[t.value] = DispatchResult(q[:n], h[:n], qi[:n], qs)
-        return t.value
+        return self._queue("yrss_fanout_submit", n, lambda outs, t: self._lib.yrss_fanout_submit(
+            self._f, _ptr(mb), n, *outs, 0, t))
 
     def submit_frames(self, data_ptrs: np.ndarray, lens: np.ndarray) -> int:
         dp = np.ascontiguousarray(data_ptrs, dtype=np.uint64)
         ln = np.ascontiguousarray(lens, dtype=np.uint16)
         n = int(dp.size)
-        q, h, qi, qs = self._outs(n)
-        t = ctypes.c_uint64()
-        abi.check(self._lib.yrss_fanout_submit_frames(self._f, _ptr(dp), _ptr(ln), n, _ptr(q),
-                                                      _ptr(h), _ptr(qi), _ptr(qs),
-                                                      ctypes.byref(t)),
-                  "yrss_fanout_submit_frames")
-        self._res[t.value] = DispatchResult(q[:n], h[:n], qi[:n], qs)
-        return t.value
+        return self._queue(
+            "yrss_fanout_submit_frames", n,
+            lambda outs, t: self._lib.yrss_fanout_submit_frames(self._f, _ptr(dp), _ptr(ln), n,
+                                                                *outs, t))
 
     def next(self, wait: bool = True):
         """(ticket, DispatchResult) of the oldest outstanding burst once done;

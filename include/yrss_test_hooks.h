@@ -36,6 +36,12 @@ int yrss_debug_line_groups(yrss_ctx *ctx, uint32_t groups, int skip_host_check);
  * 0: streaming stores like every other line (results unchanged). */
 int yrss_debug_partial_merge(yrss_ctx *ctx, int on);
 
+/* The device and pinned host buffers the library holds right now, over every
+ * context of the process: one more with each allocation, one fewer with each
+ * free.  0 once every context is closed (a context closed after a GPU timeout
+ * keeps its buffers, and its count, for the life of the process). */
+int64_t yrss_debug_live_buffers(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@
 #include <time.h>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -3083,6 +3084,85 @@ __global__ __launch_bounds__(256) void yrss_synth(yrss_synth_params p, uint64_t 
 // Host side
 // ===========================================================================
 
+namespace {
+
+int hip_fail(const char *what, hipError_t e)
+{
+    fprintf(stderr, "yrss: %s failed: %s\n", what, hipGetErrorString(e));
+    return -EIO;
+}
+
+#define YRSS_HIP(call)                                   \
+    do {                                                 \
+        hipError_t e_ = (call);                          \
+        if (e_ != hipSuccess)                            \
+            return hip_fail(#call, e_);                  \
+    } while (0)
+
+// The device and pinned host memory of a context.  A
+// buffer only holds its pointers; the group it is allocated into (BufOwner)
+// records the allocation, and release() frees the whole group.  Nothing else
+// frees: no type here has a destructor, so a context deleted without
+// release() (yrss_fini after a GPU timeout) leaves its memory to process exit.
+#ifdef YRSS_TEST_HOOKS
+int64_t g_live_buffers = 0;   // yrss_debug_live_buffers
+#define YRSS_LIVE(d) (void)__atomic_fetch_add(&g_live_buffers, (int64_t)(d), __ATOMIC_RELAXED)
+#else
+#define YRSS_LIVE(d) (void)0
+#endif
+
+struct BufOwner {
+    struct Held { void *p; bool pinned; };
+    std::vector<Held> held;
+    void keep(void *p, bool pinned)
+    {
+        held.push_back({p, pinned});
+        YRSS_LIVE(1);
+    }
+    void release()
+    {
+        for (const Held &b : held)
+            (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
+        YRSS_LIVE(-(int64_t)held.size());
+        held.clear();
+    }
+    // forgets the group without freeing it: a kernel may still be using it
+    void abandon() { held.clear(); }
+};
+
+template <class T> struct DevBuf {
+    T *d = nullptr;
+    hipError_t alloc(BufOwner &o, size_t count)
+    {
+        const hipError_t e = hipMalloc((void **)&d, count * sizeof(T));
+        if (e == hipSuccess)
+            o.keep(d, false);
+        return e;
+    }
+};
+
+template <class T> struct PinnedBuf {
+    T *h = nullptr;    // the host's address
+    T *dh = nullptr;   // the same bytes as a kernel addresses them
+    hipError_t alloc(BufOwner &o, size_t count, unsigned flags)
+    {
+        const hipError_t e = hipHostMalloc((void **)&h, count * sizeof(T), flags);
+        if (e != hipSuccess)
+            return e;
+        o.keep(h, true);
+        return hipHostGetDevicePointer((void **)&dh, h, 0);
+    }
+};
+
+// Pinned staging and its device twin: h and dh for the one-launch kernels,
+// which work on the host's copy in place, d for the grid launches.
+template <class T> struct Staged : PinnedBuf<T>, DevBuf<T> {
+    using PinnedBuf<T>::alloc;   // (owner, count, flags)
+    using DevBuf<T>::alloc;      // (owner, count)
+};
+
+}  // namespace
+
 struct TimedPair {
     hipEvent_t a, b;
     int kernel;
@@ -3125,7 +3205,6 @@ struct yrss_ctx {
     bool kni_enable = false;
     bool kni_accept = false;
     uint8_t kni_bm[2 * 8192] = {};   // tcp bitmap then udp bitmap, htons-indexed
-    uint32_t *d_kni = nullptr;
     struct Occ {
         const void *fn;
         uint32_t block, lds, blocks;
@@ -3134,61 +3213,43 @@ struct yrss_ctx {
     // The lists' workspace: per-chunk counts and prefixes, totals, scan
     // status, ranks.
     struct ListWs {
-        uint32_t *seg_cnt = nullptr;
-        uint32_t *seg_off = nullptr;
-        uint32_t *totals = nullptr;
-        unsigned long long *scan_status = nullptr;   // [nb][kMaxChunks / kScanTile]
+        BufOwner own, rank_own;      // (the ranks are regrown on their own)
+        DevBuf<uint32_t> seg_cnt, seg_off, totals;
+        DevBuf<unsigned long long> scan_status;   // [nb][kMaxChunks / kScanTile]
         uint32_t scan_epoch = 0;
-        uint16_t *rank = nullptr;    // n x u16, grown on demand
+        DevBuf<uint16_t> rank;       // n x u16, grown on demand
         size_t rank_cap = 0;
         // in-scatter prefixes: two sets of totals and range bins (the parse
         // kernel adds to set tot_set, its line scatter zeroes the other for
         // the next batch)
-        uint32_t *tot_acc = nullptr;            // [2][nb]
+        DevBuf<uint32_t> tot_acc;               // [2][nb]
         uint32_t tot_set = 0;
-        uint32_t *rbin = nullptr;               // [2][kLbMaxWgs][nb]
+        DevBuf<uint32_t> rbin;                  // [2][kLbMaxWgs][nb]
     };
     ListWs ws;
-    uint32_t *d_fault_rec = nullptr;    // host-coherent fault record {code, kernel, where, value}
-    // host-burst staging (pinned) and its device mirror
+    // what lives as long as the context
+    BufOwner own;
+    PinnedBuf<uint32_t> fault_rec;  // host-coherent fault record {code, kernel, where, value}
+    DevBuf<uint32_t> kni;
+    Staged<uint32_t> fault;         // zero-copy gather fault word (h host-coherent)
+    PinnedBuf<uint64_t> done;       // host-coherent completion word of yrss_burst_small
+    uint64_t done_seq = 0;
     hipStream_t stream = nullptr;
-    uint32_t burst_cap = 0;
-    uint8_t *h_win = nullptr;
-    uint16_t *h_len = nullptr;
-    int16_t *h_q = nullptr;
-    uint32_t *h_hash = nullptr;
-    uint32_t *h_qidx = nullptr;
-    uint32_t *h_qstart = nullptr;
-    int8_t *h_filter = nullptr;
-    uint8_t *d_win = nullptr;
-    uint16_t *d_len = nullptr;
-    int16_t *d_q = nullptr;
-    uint32_t *d_hash = nullptr;
-    uint32_t *d_qidx = nullptr;
-    uint32_t *d_qstart = nullptr;
-    int8_t *d_filter = nullptr;
-    // zero-copy: registered host ranges, device pointer array and fault word
+    // host-burst staging, grown to the largest burst seen (ensure_burst)
+    struct Staging {
+        BufOwner own;
+        uint32_t cap = 0;
+        Staged<uint8_t> win;
+        Staged<uint16_t> len;
+        Staged<int16_t> q;
+        Staged<uint32_t> hash, qidx, qstart;
+        Staged<int8_t> filter;
+        Staged<uint64_t> ptrs;      // zero-copy: the caller's pointer array
+    } st;
+    // zero-copy: registered host ranges
     uint32_t nranges = 0;
     HostRange ranges[YRSS_MAX_HOST_RANGES] = {};
     void *range_base[YRSS_MAX_HOST_RANGES] = {};
-    uint64_t *h_ptrs = nullptr;
-    uint64_t *d_ptrs = nullptr;
-    uint32_t *d_fault = nullptr;
-    uint32_t *h_fault = nullptr;    // host-coherent
-    uint64_t *h_done = nullptr;     // host-coherent completion word of yrss_burst_small
-    uint64_t *dh_done = nullptr;
-    uint64_t done_seq = 0;
-    // device views of the pinned staging: the small-burst kernel reads and
-    // writes it in place (no copies)
-    uint8_t *dh_win = nullptr;
-    uint16_t *dh_len = nullptr;
-    int16_t *dh_q = nullptr;
-    uint32_t *dh_hash = nullptr;
-    uint32_t *dh_qidx = nullptr;
-    uint32_t *dh_qstart = nullptr;
-    int8_t *dh_filter = nullptr;
-    uint64_t *dh_ptrs = nullptr;
-    uint32_t *dh_fault = nullptr;
     PendingBurst pend;
     // persistent burst worker (yrss_worker_*)
     struct WorkerState {
@@ -3201,31 +3262,32 @@ struct yrss_ctx {
         uint64_t idle_ticks = 0, life_ticks = 0;
         uint32_t poll_sleep = 1;
         hipStream_t stream = nullptr;
-        WorkerSlot *slots = nullptr, *d_slots = nullptr;   // host-coherent
-        uint64_t *done = nullptr, *d_done = nullptr;       // host-coherent
-        uint32_t *fault = nullptr;                         // device [nblocks]
-        uint32_t *brec = nullptr;                          // device [nblocks][4]
-        uint32_t *srec = nullptr, *d_srec = nullptr;       // host-coherent [nslots][4]
-        uint64_t *ptrs = nullptr, *d_ptrs = nullptr;       // pinned
-        uint16_t *lens = nullptr, *d_lens = nullptr;       // pinned (frames mode)
-        int16_t *q = nullptr, *d_q = nullptr;
-        uint32_t *hash = nullptr, *d_hash = nullptr;
-        uint32_t *qidx = nullptr, *d_qidx = nullptr;
-        uint32_t *qstart = nullptr, *d_qstart = nullptr;
-        uint64_t *next = nullptr, *d_next = nullptr;       // host-coherent
-        WorkerCtl *ctl = nullptr, *d_ctl = nullptr;        // host-coherent
-        uint8_t *win = nullptr;                            // device scratch
-        uint16_t *len = nullptr;
+        BufOwner own;
+        PinnedBuf<WorkerSlot> slots;               // host-coherent
+        PinnedBuf<uint64_t> done;                  // host-coherent
+        DevBuf<uint32_t> fault;                    // [nblocks]
+        DevBuf<uint32_t> brec;                     // [nblocks][4]
+        PinnedBuf<uint32_t> srec;                  // host-coherent [nslots][4]
+        PinnedBuf<uint64_t> ptrs;
+        PinnedBuf<uint16_t> lens;                  // (frames mode)
+        PinnedBuf<int16_t> q;                      // the slots' output staging
+        PinnedBuf<uint32_t> hash, qidx, qstart;
+        PinnedBuf<uint64_t> next;                  // host-coherent
+        PinnedBuf<WorkerCtl> ctl;                  // host-coherent
+        DevBuf<uint8_t> win;                       // scratch
+        DevBuf<uint16_t> len;
         uint64_t issued = 0;       // last ticket handed out
         uint32_t pending = 0;      // submitted, not yet polled
-        uint64_t *last_out = nullptr;   // [nslots][4] output addresses of each slot's last burst
+        // host only: [nslots][4] output addresses of each slot's last burst
+        std::unique_ptr<uint64_t[]> last_out;
         struct Out {
             int16_t *q;
             uint32_t *hash, *qidx, *qstart;
             uint32_t n;
             bool collected;
             uint8_t copy;          // bit k: output k comes from the slot's staging
-        } *out = nullptr;          // [nslots]
+        };
+        std::unique_ptr<Out[]> out;   // host only: [nslots]
     } w;
     // yrss_toeplitz_dispatch through the worker: one registered window slot
     uint8_t *shim_win = nullptr;
@@ -3244,8 +3306,8 @@ struct yrss_ctx {
     uint32_t launches[YRSS_K_COUNT] = {0, 0, 0};
     std::vector<float> durs[YRSS_K_COUNT];   // per-launch ms since yrss_timing_enable
     // A call on this context saw the GPU not finish its work (-ETIMEDOUT):
-    // yrss_fini then neither waits for the device nor frees memory a running
-    // kernel may still touch (the allocations are left to process exit).
+    // yrss_fini then neither waits for the device nor releases a BufOwner (a
+    // running kernel may still touch the memory; it is left to process exit).
     bool hung = false;
     // Test hooks (set only through the yrss_debug_* entry points of a
     // -DYRSS_TEST_HOOKS build, libyrss_test.so; always 0 in libyrss.so).
@@ -3258,19 +3320,6 @@ struct yrss_ctx {
 };
 
 namespace {
-
-int hip_fail(const char *what, hipError_t e)
-{
-    fprintf(stderr, "yrss: %s failed: %s\n", what, hipGetErrorString(e));
-    return -EIO;
-}
-
-#define YRSS_HIP(call)                                   \
-    do {                                                 \
-        hipError_t e_ = (call);                          \
-        if (e_ != hipSuccess)                            \
-            return hip_fail(#call, e_);                  \
-    } while (0)
 
 constexpr uint32_t kParseBlock = 512;   // 8 waves: one workgroup per CU (LDS)
 
@@ -3457,8 +3506,8 @@ ParseKernel pick_parse(int count, bool filter)
 ParseParams parse_params(const yrss_ctx *c, int route_lq, bool out16)
 {
     ParseParams P = c->proto;
-    P.fault = c->d_fault_rec;
-    P.kni_bm = c->d_kni;
+    P.fault = c->fault_rec.dh;
+    P.kni_bm = c->kni.d;
     P.kni_enable = c->kni_enable ? 1u : 0u;
     P.out16 = out16 ? 1u : 0u;
     if (route_lq >= 0) {
@@ -3559,60 +3608,43 @@ void kni_parse_ports(const char *p, uint8_t *bm)
 
 void free_burst(yrss_ctx *c)
 {
-    (void)hipHostFree(c->h_win); (void)hipHostFree(c->h_len); (void)hipHostFree(c->h_q);
-    (void)hipHostFree(c->h_hash); (void)hipHostFree(c->h_qidx); (void)hipHostFree(c->h_qstart);
-    (void)hipHostFree(c->h_filter);
-    (void)hipHostFree(c->h_ptrs);
-    (void)hipFree(c->d_ptrs);
-    c->h_ptrs = nullptr;
-    c->d_ptrs = nullptr;
-    (void)hipFree(c->d_win); (void)hipFree(c->d_len); (void)hipFree(c->d_q);
-    (void)hipFree(c->d_hash); (void)hipFree(c->d_qidx); (void)hipFree(c->d_qstart);
-    (void)hipFree(c->d_filter);
-    c->h_win = nullptr; c->h_len = nullptr; c->h_q = nullptr; c->h_hash = nullptr;
-    c->h_qidx = nullptr; c->h_qstart = nullptr; c->h_filter = nullptr;
-    c->d_win = nullptr; c->d_len = nullptr; c->d_q = nullptr; c->d_hash = nullptr;
-    c->d_qidx = nullptr; c->d_qstart = nullptr; c->d_filter = nullptr;
-    c->burst_cap = 0;
+    c->st.own.release();
+    c->st = yrss_ctx::Staging{};
 }
 
 int ensure_burst(yrss_ctx *c, uint32_t n)
 {
-    if (n <= c->burst_cap)
+    yrss_ctx::Staging &st = c->st;
+    if (n <= st.cap)
         return 0;
     free_burst(c);
-    const uint32_t cap = std::max<uint32_t>(n, 1024u);
+    const size_t cap = std::max<uint32_t>(n, 1024u);
     const size_t nbk = (size_t)c->nb + 3;   // (the routed lists: nb_queues + 4 offsets)
-    YRSS_HIP(hipHostMalloc((void **)&c->h_win, (size_t)cap * YRSS_WIN_FULL, hipHostMallocDefault));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_len, (size_t)cap * 2, hipHostMallocDefault));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_q, (size_t)cap * 2, hipHostMallocDefault));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_hash, (size_t)cap * 4, hipHostMallocDefault));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_qidx, (size_t)cap * 4, hipHostMallocDefault));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_qstart, nbk * 4, hipHostMallocDefault));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_filter, (size_t)cap, hipHostMallocDefault));
-    YRSS_HIP(hipMalloc((void **)&c->d_win, (size_t)cap * YRSS_WIN_FULL));
-    YRSS_HIP(hipMalloc((void **)&c->d_len, (size_t)cap * 2));
-    YRSS_HIP(hipMalloc((void **)&c->d_q, (size_t)cap * 2));
-    YRSS_HIP(hipMalloc((void **)&c->d_hash, (size_t)cap * 4));
-    YRSS_HIP(hipMalloc((void **)&c->d_qidx, (size_t)cap * 4));
-    YRSS_HIP(hipMalloc((void **)&c->d_qstart, nbk * 4));
-    YRSS_HIP(hipMalloc((void **)&c->d_filter, (size_t)cap));
-    YRSS_HIP(hipHostMalloc((void **)&c->h_ptrs, (size_t)cap * 8, hipHostMallocDefault));
-    YRSS_HIP(hipMalloc((void **)&c->d_ptrs, (size_t)cap * 8));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_win, c->h_win, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_len, c->h_len, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_q, c->h_q, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_hash, c->h_hash, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_qidx, c->h_qidx, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_qstart, c->h_qstart, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_filter, c->h_filter, 0));
-    YRSS_HIP(hipHostGetDevicePointer((void **)&c->dh_ptrs, c->h_ptrs, 0));
-    c->burst_cap = cap;
+    const unsigned pin = hipHostMallocDefault;
+    hipError_t e;
+    if ((e = st.win.alloc(st.own, cap * YRSS_WIN_FULL, pin)) != hipSuccess ||
+        (e = st.len.alloc(st.own, cap, pin)) != hipSuccess ||
+        (e = st.q.alloc(st.own, cap, pin)) != hipSuccess ||
+        (e = st.hash.alloc(st.own, cap, pin)) != hipSuccess ||
+        (e = st.qidx.alloc(st.own, cap, pin)) != hipSuccess ||
+        (e = st.qstart.alloc(st.own, nbk, pin)) != hipSuccess ||
+        (e = st.filter.alloc(st.own, cap, pin)) != hipSuccess ||
+        (e = st.win.alloc(st.own, cap * YRSS_WIN_FULL)) != hipSuccess ||
+        (e = st.len.alloc(st.own, cap)) != hipSuccess ||
+        (e = st.q.alloc(st.own, cap)) != hipSuccess ||
+        (e = st.hash.alloc(st.own, cap)) != hipSuccess ||
+        (e = st.qidx.alloc(st.own, cap)) != hipSuccess ||
+        (e = st.qstart.alloc(st.own, nbk)) != hipSuccess ||
+        (e = st.filter.alloc(st.own, cap)) != hipSuccess ||
+        (e = st.ptrs.alloc(st.own, cap, pin)) != hipSuccess ||
+        (e = st.ptrs.alloc(st.own, cap)) != hipSuccess)
+        return hip_fail("burst staging allocation", e);   // (cap stays 0: freed by the next call)
+    st.cap = (uint32_t)cap;
     return 0;
 }
 
 // Host-staged classification shared by the burst/frames/route entry points.
-// The windows and data_len are already gathered into c->h_win / c->h_len at
+// The windows and data_len are already gathered into c->st.win.h / c->st.len.h at
 // stride W; results land in the caller's host arrays (NULL = not wanted).
 // hipHostRegister is process-wide, but each context keeps its own range table
 // (several contexts pipeline bursts over one mbuf pool), so registrations are
@@ -3707,7 +3739,7 @@ const char *fault_name(uint32_t code)
 // record to *out (if given) and clears it.  The caller has synchronised.
 bool take_fault(yrss_ctx *c, yrss_fault *out = nullptr)
 {
-    uint32_t *r = c->d_fault_rec;
+    uint32_t *r = c->fault_rec.h;
     const yrss_fault f{__atomic_load_n(r, __ATOMIC_ACQUIRE), r[1], r[2], r[3]};
     if (out)
         *out = f;
@@ -3726,36 +3758,30 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
 // the columns of the launch)
 hipError_t list_ws_alloc(yrss_ctx *c, yrss_ctx::ListWs &w)
 {
-    const size_t cnt = (size_t)kMaxChunks * c->nb * sizeof(uint32_t);
-    const size_t st = (size_t)c->nb * (kMaxChunks / kScanTile) * sizeof(unsigned long long);
+    const size_t cnt = (size_t)kMaxChunks * c->nb;
+    const size_t st = (size_t)c->nb * (kMaxChunks / kScanTile);
+    const size_t rb = 2u * kLbMaxWgs * c->nb;
     hipError_t e;
-    if ((e = hipMalloc((void **)&w.seg_cnt, cnt)) != hipSuccess ||
-        (e = hipMalloc((void **)&w.seg_off, cnt)) != hipSuccess ||
-        (e = hipMalloc((void **)&w.totals, c->nb * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&w.scan_status, st)) != hipSuccess ||
-        (e = hipMemset(w.scan_status, 0, st)) != hipSuccess ||
-        (e = hipMemset(w.seg_cnt, 0, cnt)) != hipSuccess)
+    if ((e = w.seg_cnt.alloc(w.own, cnt)) != hipSuccess ||
+        (e = w.seg_off.alloc(w.own, cnt)) != hipSuccess ||
+        (e = w.totals.alloc(w.own, c->nb)) != hipSuccess ||
+        (e = w.scan_status.alloc(w.own, st)) != hipSuccess ||
+        (e = hipMemset(w.scan_status.d, 0, st * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(w.seg_cnt.d, 0, cnt * sizeof(uint32_t))) != hipSuccess)
         return e;
-    if (c->nb <= kFusedMaxNb) {
-        const size_t rb = 2u * kLbMaxWgs * c->nb * sizeof(uint32_t);
-        if ((e = hipMalloc((void **)&w.tot_acc, 2u * c->nb * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMemset(w.tot_acc, 0, 2u * c->nb * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&w.rbin, rb)) != hipSuccess ||
-            (e = hipMemset(w.rbin, 0, rb)) != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+    if (c->nb > kFusedMaxNb)
+        return hipSuccess;
+    if ((e = w.tot_acc.alloc(w.own, 2u * c->nb)) != hipSuccess ||
+        (e = hipMemset(w.tot_acc.d, 0, 2u * c->nb * sizeof(uint32_t))) != hipSuccess ||
+        (e = w.rbin.alloc(w.own, rb)) != hipSuccess)
+        return e;
+    return hipMemset(w.rbin.d, 0, rb * sizeof(uint32_t));
 }
 
 void list_ws_free(yrss_ctx::ListWs &w)
 {
-    (void)hipFree(w.seg_cnt);
-    (void)hipFree(w.seg_off);
-    (void)hipFree(w.totals);
-    (void)hipFree(w.scan_status);
-    (void)hipFree(w.tot_acc);
-    (void)hipFree(w.rbin);
-    (void)hipFree(w.rank);
+    w.own.release();
+    w.rank_own.release();
     w = yrss_ctx::ListWs{};
 }
 
@@ -3784,7 +3810,7 @@ int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = tru
                  hipStream_t stream = nullptr, bool route = false)
 {
     if (host_burst) {
-        S.done = c->dh_done;
+        S.done = c->done.dh;
         S.seq = ++c->done_seq;
         c->pend.done_seq = S.seq;   // the caller reset pend before
         stream = c->stream;
@@ -3818,7 +3844,7 @@ int finish_burst(yrss_ctx *c)
     if (p.done_seq) {
         const uint64_t t0 = mono_ns();
         for (uint32_t k = 1;; ++k) {
-            if (__atomic_load_n(c->h_done, __ATOMIC_ACQUIRE) == p.done_seq) {
+            if (__atomic_load_n(c->done.h, __ATOMIC_ACQUIRE) == p.done_seq) {
                 done = true;
                 break;
             }
@@ -3829,7 +3855,7 @@ int finish_burst(yrss_ctx *c)
     }
     if (!done)
         YRSS_HIP(hipStreamSynchronize(c->stream));
-    if (p.gather_fault && __atomic_load_n(c->h_fault, __ATOMIC_ACQUIRE))
+    if (p.gather_fault && __atomic_load_n(c->fault.h, __ATOMIC_ACQUIRE))
         return -EFAULT;
     if (p.dev_fault && take_fault(c))
         return -EIO;
@@ -3879,11 +3905,11 @@ PendingBurst &pend_setup(yrss_ctx *c, uint32_t n, int16_t *out_q, uint32_t *out_
     PendingBurst &p = c->pend;
     p = PendingBurst{};
     p.n = n;
-    p.outs[0] = {out_q, c->h_q, (size_t)n * 2, false};
-    p.outs[1] = {out_hash, c->h_hash, (size_t)n * 4, false};
-    p.outs[2] = {compact ? out_qidx : nullptr, c->h_qidx, (size_t)n * 4, false};
-    p.outs[3] = {compact ? out_qstart : nullptr, c->h_qstart, (size_t)noff * 4, false};
-    p.outs[4] = {out_filter, c->h_filter, n, false};
+    p.outs[0] = {out_q, c->st.q.h, (size_t)n * 2, false};
+    p.outs[1] = {out_hash, c->st.hash.h, (size_t)n * 4, false};
+    p.outs[2] = {compact ? out_qidx : nullptr, c->st.qidx.h, (size_t)n * 4, false};
+    p.outs[3] = {compact ? out_qstart : nullptr, c->st.qstart.h, (size_t)noff * 4, false};
+    p.outs[4] = {out_filter, c->st.filter.h, n, false};
     return p;
 }
 
@@ -3895,15 +3921,15 @@ int staged_dev_batch(yrss_ctx *c, uint32_t W, bool want_hash)
     const PendingBurst &p = c->pend;
     const bool compact = p.outs[2].user != nullptr;
     yrss_dev_batch b;
-    b.win = c->d_win;
+    b.win = c->st.win.d;
     b.win_stride = W;
     b.n = p.n;
-    b.len = c->d_len;
-    b.q = c->d_q;
-    b.hash = want_hash ? c->d_hash : nullptr;
-    b.qidx = compact ? c->d_qidx : nullptr;
-    b.qstart = compact ? c->d_qstart : nullptr;
-    b.filter = p.outs[4].user ? c->d_filter : nullptr;
+    b.len = c->st.len.d;
+    b.q = c->st.q.d;
+    b.hash = want_hash ? c->st.hash.d : nullptr;
+    b.qidx = compact ? c->st.qidx.d : nullptr;
+    b.qstart = compact ? c->st.qstart.d : nullptr;
+    b.filter = p.outs[4].user ? c->st.filter.d : nullptr;
     return dispatch_dev_impl(c, &b, c->stream);
 }
 
@@ -3914,7 +3940,7 @@ int staged_dev_batch(yrss_ctx *c, uint32_t W, bool want_hash)
 int staged_copy_back(yrss_ctx *c, bool stage_hash)
 {
     PendingBurst &p = c->pend;
-    const void *src[5] = {c->d_q, c->d_hash, c->d_qidx, c->d_qstart, c->d_filter};
+    const void *src[5] = {c->st.q.d, c->st.hash.d, c->st.qidx.d, c->st.qstart.d, c->st.filter.d};
     for (int k = 0; k < 5; ++k) {
         if (!p.outs[k].user && !(k == 1 && stage_hash))
             continue;
@@ -3926,8 +3952,8 @@ int staged_copy_back(yrss_ctx *c, bool stage_hash)
     return 0;
 }
 
-// Queues the classification of windows already gathered into c->h_win /
-// c->h_len at stride W; results go to the caller's host arrays (NULL = not
+// Queues the classification of windows already gathered into c->st.win.h /
+// c->st.len.h at stride W; results go to the caller's host arrays (NULL = not
 // wanted) when the burst completes (finish_burst).  want_hash computes the
 // hash into the staging even without out_hash (hash.rss write-back).
 // route_lq >= 0 (yrss_route_lists_*; the caller checked n and nb_queues): the
@@ -3946,23 +3972,23 @@ int classify_staged(yrss_ctx *c, uint32_t n, uint32_t W, int16_t *out_q, uint32_
     if (route || small_ok(c, n)) {
         // the kernel reads the staged windows and writes the staging in place
         SmallParams S = small_params(c, route_lq);
-        S.P.win = c->dh_win;
-        S.P.len = c->dh_len;
+        S.P.win = c->st.win.dh;
+        S.P.len = c->st.len.dh;
         S.P.stride = W;
         S.P.n = n;
-        S.P.q = c->dh_q;
-        S.P.hash = want_hash ? c->dh_hash : nullptr;
-        S.P.filter = out_filter ? c->dh_filter : nullptr;
-        S.qidx = compact ? c->dh_qidx : nullptr;
-        S.qstart = compact ? c->dh_qstart : nullptr;
+        S.P.q = c->st.q.dh;
+        S.P.hash = want_hash ? c->st.hash.dh : nullptr;
+        S.P.filter = out_filter ? c->st.filter.dh : nullptr;
+        S.qidx = compact ? c->st.qidx.dh : nullptr;
+        S.qstart = compact ? c->st.qstart.dh : nullptr;
         int rc = small_launch(c, S, out_filter != nullptr, true, nullptr, route);
         if (rc)
             return rc;
         p.active = true;
         return 0;
     }
-    YRSS_HIP(hipMemcpyAsync(c->d_win, c->h_win, (size_t)n * W, hipMemcpyHostToDevice, s));
-    YRSS_HIP(hipMemcpyAsync(c->d_len, c->h_len, (size_t)n * 2, hipMemcpyHostToDevice, s));
+    YRSS_HIP(hipMemcpyAsync(c->st.win.d, c->st.win.h, (size_t)n * W, hipMemcpyHostToDevice, s));
+    YRSS_HIP(hipMemcpyAsync(c->st.len.d, c->st.len.h, (size_t)n * 2, hipMemcpyHostToDevice, s));
     int rc = staged_dev_batch(c, W, want_hash);
     return rc ? rc : staged_copy_back(c, want_hash);
 }
@@ -3993,7 +4019,7 @@ int gather_mbufs(yrss_ctx *c, void *const *mbufs, uint32_t n, uint32_t *W_out)
     // window's address is kept in the pinned pointer scratch), the second
     // copies the windows.  Each pass prefetches kGatherAhead packets ahead.
     constexpr uint32_t kGatherAhead = 16;
-    const uint8_t **src = reinterpret_cast<const uint8_t **>(c->h_ptrs);
+    const uint8_t **src = reinterpret_cast<const uint8_t **>(c->st.ptrs.h);
     uint32_t maxlen = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (i + kGatherAhead < n)
@@ -4005,7 +4031,7 @@ int gather_mbufs(yrss_ctx *c, void *const *mbufs, uint32_t n, uint32_t *W_out)
         memcpy(&doff, m + ml.off_data_off, 2);
         memcpy(&L, m + ml.off_data_len, 2);
         src[i] = buf + doff;
-        c->h_len[i] = L;
+        c->st.len.h[i] = L;
         maxlen = std::max<uint32_t>(maxlen, L);
     }
     const uint32_t W = host_stride(maxlen);
@@ -4014,8 +4040,8 @@ int gather_mbufs(yrss_ctx *c, void *const *mbufs, uint32_t n, uint32_t *W_out)
             __builtin_prefetch(src[i + kGatherAhead]);
             __builtin_prefetch(src[i + kGatherAhead] + W - 1);
         }
-        const uint32_t L = c->h_len[i];
-        memcpy(c->h_win + (size_t)i * W, src[i], L < W ? L : W);
+        const uint32_t L = c->st.len.h[i];
+        memcpy(c->st.win.h + (size_t)i * W, src[i], L < W ? L : W);
     }
     *W_out = W;
     return 0;
@@ -4036,8 +4062,8 @@ int gather_frames(yrss_ctx *c, const uint8_t *const *data, const uint16_t *len, 
         if (i + 16u < n)
             __builtin_prefetch(data[i + 16u]);
         const uint32_t L = len[i];
-        memcpy(c->h_win + (size_t)i * W, data[i], L < W ? L : W);
-        c->h_len[i] = (uint16_t)L;
+        memcpy(c->st.win.h + (size_t)i * W, data[i], L < W ? L : W);
+        c->st.len.h[i] = (uint16_t)L;
     }
     *W_out = W;
     return 0;
@@ -4188,22 +4214,19 @@ int yrss_init(const struct yrss_config *cfg, yrss_ctx **out)
 
     hipError_t e;
     if ((e = list_ws_alloc(c, c->ws)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&c->d_fault_rec, 64, hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_kni, sizeof(c->kni_bm))) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_fault, sizeof(uint32_t))) != hipSuccess ||
-        (e = hipHostMalloc((void **)&c->h_fault, sizeof(uint32_t), hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&c->dh_fault, c->h_fault, 0)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&c->h_done, 64, hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&c->dh_done, c->h_done, 0)) != hipSuccess ||
-        (e = hipMemset(c->d_kni, 0, sizeof(c->kni_bm))) != hipSuccess ||
+        (e = c->fault_rec.alloc(c->own, 16, hipHostMallocCoherent)) != hipSuccess ||   // 64 B
+        (e = c->kni.alloc(c->own, sizeof(c->kni_bm) / sizeof(uint32_t))) != hipSuccess ||
+        (e = c->fault.alloc(c->own, 1)) != hipSuccess ||
+        (e = c->fault.alloc(c->own, 1, hipHostMallocCoherent)) != hipSuccess ||
+        (e = c->done.alloc(c->own, 8, hipHostMallocCoherent)) != hipSuccess ||        // 64 B
+        (e = hipMemset(c->kni.d, 0, sizeof(c->kni_bm))) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming)) != hipSuccess) {
         yrss_fini(c);
         return hip_fail("yrss_init allocation", e);
     }
-    memset(c->d_fault_rec, 0, 64);
-    *c->h_done = 0;
+    memset(c->fault_rec.h, 0, 64);
+    *c->done.h = 0;
     // The memsets above run on the null stream, which does not order against
     // the context's non-blocking stream: without this wait a first dispatch
     // could race the zeroing of the count matrix (seen once on the GPU box as
@@ -4235,14 +4258,18 @@ void yrss_fini(yrss_ctx *c)
         // would block here as well.  Ask a resident worker to leave, keep
         // every device and pinned allocation (a kernel still running may
         // write them), and free only what the host alone uses.
-        if (c->w.on && c->w.ctl)
-            __atomic_store_n(&c->w.ctl->stop, 1u, __ATOMIC_RELEASE);
+        if (c->w.on && c->w.ctl.h)
+            __atomic_store_n(&c->w.ctl.h->stop, 1u, __ATOMIC_RELEASE);
         fprintf(stderr, "yrss: context closed after a GPU timeout: not drained, device memory "
                         "left to process exit\n");
         for (uint32_t r = 0; r < c->nranges; ++r)
             host_reg_poison(c->range_base[r]);
-        delete[] c->w.out;
-        delete[] c->w.last_out;
+        // Device and pinned memory is freed by BufOwner::release() and by
+        // nothing else; every owner of the context is told to forget its
+        // buffers instead, and delete frees the host-only rest (the owners'
+        // records, the worker's two per-slot arrays).
+        for (BufOwner *o : {&c->own, &c->st.own, &c->ws.own, &c->ws.rank_own, &c->w.own})
+            o->abandon();
         delete c;   // (shim_win stays: it may be registered for the GPU to read)
         return;
     }
@@ -4262,11 +4289,7 @@ void yrss_fini(yrss_ctx *c)
         (void)hipEventDestroy(e);
     free_burst(c);
     list_ws_free(c->ws);
-    (void)hipHostFree(c->d_fault_rec);
-    (void)hipFree(c->d_kni);
-    (void)hipFree(c->d_fault);
-    (void)hipHostFree(c->h_fault);
-    (void)hipHostFree(c->h_done);
+    c->own.release();
     for (uint32_t r = 0; r < c->nranges; ++r)
         host_reg_release(c->range_base[r]);
     free(c->shim_win);
@@ -4311,7 +4334,7 @@ int yrss_set_kni(yrss_ctx *c, int enable, const char *method, const char *tcp_po
     c->kni_enable = enable != 0;
     c->kni_accept = accept;
     YRSS_HIP(hipSetDevice(c->device));
-    YRSS_HIP(hipMemcpy(c->d_kni, c->kni_bm, sizeof(c->kni_bm), hipMemcpyHostToDevice));
+    YRSS_HIP(hipMemcpy(c->kni.d, c->kni_bm, sizeof(c->kni_bm), hipMemcpyHostToDevice));
     YRSS_HIP(hipDeviceSynchronize());   // ordered before any stream's next dispatch
     return 0;
 }
@@ -4442,13 +4465,13 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     if (ranked && W.rank_cap < n) {
         // the ranks' workspace grows to the largest batch seen; the old one
         // may still be read by a scatter queued on this stream
-        if (W.rank) {
+        if (W.rank.d) {
             YRSS_HIP(hipStreamSynchronize(s));
-            (void)hipFree(W.rank);
-            W.rank = nullptr;
+            W.rank_own.release();
+            W.rank = {};
             W.rank_cap = 0;
         }
-        YRSS_HIP(hipMalloc((void **)&W.rank, (size_t)n * sizeof(uint16_t)));
+        YRSS_HIP(W.rank.alloc(W.rank_own, n));
         W.rank_cap = n;
     }
     // The line scatter's launch, planned before the parse kernel: with
@@ -4465,7 +4488,7 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
         const uint32_t spans = (uint32_t)(((uint64_t)n + lp.seg - 1) / lp.seg);
         line_grid = std::max(1u, std::min(spans, resident_blocks(c, (const void *)line_fn,
                                                                  kLineBlock, lp.lds)));
-        if (c->nb <= kFusedMaxNb && W.tot_acc && c->tune.scan_kernel == 0) {
+        if (c->nb <= kFusedMaxNb && W.tot_acc.d && c->tune.scan_kernel == 0) {
             // ranges of rcs spans (the last ones may be shorter), rc chunks
             const uint32_t rcs_ = (spans + line_grid - 1) / line_grid;
             const uint32_t g_eff = (spans + rcs_ - 1) / rcs_;
@@ -4487,8 +4510,8 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     P.len = b->len;
     P.q = b->q;
     P.hash = b->hash;
-    P.seg_cnt = compact ? W.seg_cnt : nullptr;
-    P.rank = ranked ? W.rank : nullptr;
+    P.seg_cnt = compact ? W.seg_cnt.d : nullptr;
+    P.rank = ranked ? W.rank.d : nullptr;
     P.n = n;
     P.stride = win_stride;
     P.chunk = lay.chunk;
@@ -4498,8 +4521,8 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     P.filter = b->filter;
     P.rank_pack = ranked && lp.packed ? 1u : 0u;
     const uint32_t tset = W.tot_set;
-    P.tot_acc = fused ? W.tot_acc + (size_t)tset * c->nb : nullptr;
-    P.rbin = fused ? W.rbin + (size_t)tset * kLbMaxWgs * c->nb : nullptr;
+    P.tot_acc = fused ? W.tot_acc.d + (size_t)tset * c->nb : nullptr;
+    P.rbin = fused ? W.rbin.d + (size_t)tset * kLbMaxWgs * c->nb : nullptr;
     P.rbin_chunks = fused ? rcs << lp.gshift : 0u;
     {
         Timed t(c, YRSS_K_PARSE_HASH);
@@ -4515,11 +4538,11 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     if (!fused) {
         Timed t(c, YRSS_K_SCAN);
         ScanParams SP;
-        SP.cnt = W.seg_cnt;
-        SP.off = W.seg_off;
-        SP.totals = W.totals;
-        SP.status = W.scan_status;
-        SP.fault = c->d_fault_rec;
+        SP.cnt = W.seg_cnt.d;
+        SP.off = W.seg_off.d;
+        SP.totals = W.totals.d;
+        SP.status = W.scan_status.d;
+        SP.fault = c->fault_rec.dh;
         SP.nchunk = lay.nchunk;
         SP.ncol = lay.ncol;
         SP.sub = lay.ncol % (kScanSub * kScanTile) == 0 ? kScanSub : 1u;
@@ -4534,12 +4557,12 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     if (ranked) {
         LineParams S;
         S.q = b->q;
-        S.rank = W.rank;
-        S.seg_off = W.seg_off;
-        S.totals = W.totals;
+        S.rank = W.rank.d;
+        S.seg_off = W.seg_off.d;
+        S.totals = W.totals.d;
         S.qidx = b->qidx;
         S.qstart = b->qstart;
-        S.fault = c->d_fault_rec;
+        S.fault = c->fault_rec.dh;
         S.n = n;
         S.nq = c->cfg.nb_queues;
         S.nb = c->nb;
@@ -4554,17 +4577,17 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
         S.early = c->nb > 16u ? 1u : 0u;
         S.merge = c->dbg.partial_merge;
         S.fused = fused ? 1u : 0u;
-        S.cnt = W.seg_cnt;
+        S.cnt = W.seg_cnt.d;
         S.rbin = nullptr;
         S.rbin_next = nullptr;
         S.rts = rts;
         S.rcs = rcs;
         S.tot_next = nullptr;
         if (fused) {
-            S.totals = W.tot_acc + (size_t)tset * c->nb;
-            S.tot_next = W.tot_acc + (size_t)(tset ^ 1u) * c->nb;
-            S.rbin = W.rbin + (size_t)tset * kLbMaxWgs * c->nb;
-            S.rbin_next = W.rbin + (size_t)(tset ^ 1u) * kLbMaxWgs * c->nb;
+            S.totals = W.tot_acc.d + (size_t)tset * c->nb;
+            S.tot_next = W.tot_acc.d + (size_t)(tset ^ 1u) * c->nb;
+            S.rbin = W.rbin.d + (size_t)tset * kLbMaxWgs * c->nb;
+            S.rbin_next = W.rbin.d + (size_t)(tset ^ 1u) * kLbMaxWgs * c->nb;
             S.xcd = 0;   // (ranges in blockIdx order: the kernel ignores it too)
         }
         Timed t(c, YRSS_K_SCATTER);
@@ -4575,11 +4598,11 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     }
     ScatterParams S;
     S.q = b->q;
-    S.seg_off = W.seg_off;
-    S.totals = W.totals;
+    S.seg_off = W.seg_off.d;
+    S.totals = W.totals.d;
     S.qidx = b->qidx;
     S.qstart = b->qstart;
-    S.fault = c->d_fault_rec;
+    S.fault = c->fault_rec.dh;
     S.n = n;
     S.seg = lay.seg;
     S.nq = c->cfg.nb_queues;
@@ -4903,6 +4926,7 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
     if ((rc = ensure_burst(c, n)) != 0)
         return rc;
     hipStream_t s = c->stream;
+    const yrss_ctx::Staging &st = c->st;
     const bool small = small_ok(c, n);
     GatherParams G;
     memset(&G, 0, sizeof(G));
@@ -4911,31 +4935,31 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
     // from the pinned staging, in place too on the small-burst path.
     G.ptrs = (const uint64_t *)dev_alias(c, ptrs, (size_t)n * 8);
     if (!G.ptrs) {
-        memcpy(c->h_ptrs, ptrs, (size_t)n * 8);
+        memcpy(st.ptrs.h, ptrs, (size_t)n * 8);
         if (small) {
-            G.ptrs = c->dh_ptrs;
+            G.ptrs = st.ptrs.dh;
         } else {
-            YRSS_HIP(hipMemcpyAsync(c->d_ptrs, c->h_ptrs, (size_t)n * 8, hipMemcpyHostToDevice,
+            YRSS_HIP(hipMemcpyAsync(st.ptrs.d, st.ptrs.h, (size_t)n * 8, hipMemcpyHostToDevice,
                                     s));
-            G.ptrs = c->d_ptrs;
+            G.ptrs = st.ptrs.d;
         }
     }
     if (frames) {
         G.lens = (const uint16_t *)dev_alias(c, lens, (size_t)n * 2);
         if (!G.lens) {
-            memcpy(c->h_len, lens, (size_t)n * 2);
+            memcpy(st.len.h, lens, (size_t)n * 2);
             if (small) {
-                G.lens = c->dh_len;
+                G.lens = st.len.dh;
             } else {
-                YRSS_HIP(hipMemcpyAsync(c->d_q, c->h_len, (size_t)n * 2, hipMemcpyHostToDevice,
+                YRSS_HIP(hipMemcpyAsync(st.q.d, st.len.h, (size_t)n * 2, hipMemcpyHostToDevice,
                                         s));
-                G.lens = (const uint16_t *)c->d_q;   // d_q is free until the parse kernel
+                G.lens = (const uint16_t *)st.q.d;   // q.d is free until the parse kernel
             }
         }
     }
-    G.win = c->d_win;
-    G.len = c->d_len;
-    G.hash = c->d_hash;
+    G.win = st.win.d;
+    G.len = st.len.d;
+    G.hash = st.hash.d;
     G.n = n;
     G.frames = frames ? 1u : 0u;
     const bool want_hash = out_hash || (flags & YRSS_F_WRITE_RSS);
@@ -4947,17 +4971,17 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
     if (small) {
         // one launch: gather + parse + lists, outputs straight to host memory
         // (the caller's arrays when registered, else the pinned staging)
-        *c->h_fault = 0;
-        G.fault = c->dh_fault;
+        *c->fault.h = 0;
+        G.fault = c->fault.dh;
         SmallParams S = small_params(c);
         S.G = G;
         S.gather = 1;
         S.writeback = (!frames && (flags & YRSS_F_WRITE_RSS)) ? 1u : 0u;
-        S.P.win = c->d_win;
-        S.P.len = c->d_len;
+        S.P.win = st.win.d;
+        S.P.len = st.len.d;
         S.P.stride = YRSS_WIN_FULL;
         S.P.n = n;
-        void *staged[4] = {c->dh_q, c->dh_hash, c->dh_qidx, c->dh_qstart};
+        void *staged[4] = {st.q.dh, st.hash.dh, st.qidx.dh, st.qstart.dh};
         void *dst[4] = {nullptr, nullptr, nullptr, nullptr};
         for (int k = 0; k < 4; ++k)
             if (p.outs[k].user)
@@ -4973,8 +4997,8 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
         p.active = true;
         return 0;
     }
-    YRSS_HIP(hipMemsetAsync(c->d_fault, 0, sizeof(uint32_t), s));
-    G.fault = c->d_fault;
+    YRSS_HIP(hipMemsetAsync(c->fault.d, 0, sizeof(uint32_t), s));
+    G.fault = c->fault.d;
     const uint32_t blocks = std::min<uint32_t>((n + 63u) / 64u, (uint32_t)c->cus * 8u);
     hipLaunchKernelGGL(yrss_gather_zc, dim3(blocks), dim3(256), 0, s, G);
     YRSS_HIP(hipGetLastError());
@@ -4984,7 +5008,7 @@ int zc_dispatch(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t n,
         hipLaunchKernelGGL(yrss_writeback_zc, dim3((n + 255u) / 256u), dim3(256), 0, s, G);
         YRSS_HIP(hipGetLastError());
     }
-    YRSS_HIP(hipMemcpyAsync(c->h_fault, c->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    YRSS_HIP(hipMemcpyAsync(c->fault.h, c->fault.d, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return staged_copy_back(c, false);   // (the write-back ran on the device)
 }
 
@@ -5100,12 +5124,13 @@ int yrss_rss_lport_sweep(yrss_ctx *c, uint32_t faddr, uint32_t laddr, uint16_t f
     P.fixed[0] = faddr;
     P.fixed[1] = laddr;
     P.fixed[2] = fport;
-    P.bitmap = c->d_qidx;                     // 8 KiB of the burst staging
+    P.bitmap = c->st.qidx.d;                     // 8 KiB of the burst staging
     hipLaunchKernelGGL(yrss_rss_check, dim3(65536 / 256), dim3(256), 0, c->stream, P);
     YRSS_HIP(hipGetLastError());
-    YRSS_HIP(hipMemcpyAsync(c->h_qidx, c->d_qidx, 2048 * 4, hipMemcpyDeviceToHost, c->stream));
+    YRSS_HIP(hipMemcpyAsync(c->st.qidx.h, c->st.qidx.d, 2048 * 4, hipMemcpyDeviceToHost,
+                            c->stream));
     YRSS_HIP(hipStreamSynchronize(c->stream));
-    memcpy(bitmap, c->h_qidx, 2048 * 4);
+    memcpy(bitmap, c->st.qidx.h, 2048 * 4);
     return 0;
 }
 
@@ -5131,25 +5156,9 @@ namespace {
 void worker_free(yrss_ctx *c)
 {
     auto &w = c->w;
-    (void)hipHostFree(w.slots);
-    (void)hipHostFree(w.done);
-    (void)hipFree(w.fault);
-    (void)hipFree(w.brec);
-    (void)hipHostFree(w.srec);
-    (void)hipHostFree(w.ptrs);
-    (void)hipHostFree(w.lens);
-    (void)hipHostFree(w.q);
-    (void)hipHostFree(w.hash);
-    (void)hipHostFree(w.qidx);
-    (void)hipHostFree(w.qstart);
-    (void)hipHostFree(w.next);
-    (void)hipHostFree(w.ctl);
-    (void)hipFree(w.win);
-    (void)hipFree(w.len);
+    w.own.release();
     if (w.stream)
         (void)hipStreamDestroy(w.stream);
-    delete[] w.out;
-    delete[] w.last_out;
     w = yrss_ctx::WorkerState{};
 }
 
@@ -5161,10 +5170,10 @@ int worker_halt(yrss_ctx *c)
     auto &w = c->w;
     if (!w.running)
         return 0;
-    __atomic_store_n(&w.ctl->stop, 1u, __ATOMIC_RELEASE);
+    __atomic_store_n(&w.ctl.h->stop, 1u, __ATOMIC_RELEASE);
     const hipError_t e = hipStreamSynchronize(w.stream);
-    __atomic_store_n(&w.ctl->stop, 0u, __ATOMIC_RELEASE);
-    __atomic_store_n(&w.ctl->exited, 0u, __ATOMIC_RELAXED);
+    __atomic_store_n(&w.ctl.h->stop, 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(&w.ctl.h->exited, 0u, __ATOMIC_RELAXED);
     w.running = false;
     return e == hipSuccess ? 0 : hip_fail("worker halt", e);
 }
@@ -5182,18 +5191,18 @@ int worker_launch(yrss_ctx *c)
     if (!w.route)
         W.P.kni_enable = 0;
     gather_config(c, W.G);
-    W.slots = w.d_slots;
-    W.done = w.d_done;
-    W.fault = w.fault;
-    W.brec = w.brec;
-    W.srec = w.d_srec;
+    W.slots = w.slots.dh;
+    W.done = w.done.dh;
+    W.fault = w.fault.d;
+    W.brec = w.brec.d;
+    W.srec = w.srec.dh;
     W.inject = c->dbg.worker_inject;
-    W.ptrs = w.d_ptrs;
-    W.lens = w.d_lens;
-    W.win = w.win;
-    W.len = w.len;
-    W.next = w.d_next;
-    W.wctl = w.d_ctl;
+    W.ptrs = w.ptrs.dh;
+    W.lens = w.lens.dh;
+    W.win = w.win.d;
+    W.len = w.len.d;
+    W.next = w.next.dh;
+    W.wctl = w.ctl.dh;
     W.nslots = w.nslots;
     W.idle_ticks = w.idle_ticks;
     W.life_ticks = w.life_ticks;
@@ -5217,7 +5226,7 @@ int worker_launch(yrss_ctx *c)
 int worker_ensure(yrss_ctx *c)
 {
     auto &w = c->w;
-    if (w.running && __atomic_load_n(&w.ctl->exited, __ATOMIC_ACQUIRE) == 0u)
+    if (w.running && __atomic_load_n(&w.ctl.h->exited, __ATOMIC_ACQUIRE) == 0u)
         return 0;
     YRSS_HIP(hipSetDevice(c->device));
     const int rc = worker_halt(c);
@@ -5252,56 +5261,39 @@ int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uin
     w.idle_ticks = std::min<uint64_t>(idle_ms, 10000u) * (uint64_t)khz;
     w.life_ticks = std::min<uint64_t>(std::max<uint64_t>(life_ms, 1u), 10000u) * (uint64_t)khz;
     const size_t S = nslots, M = kWorkerMaxBurst;
+    const size_t B = nblocks;
+    const unsigned coh = hipHostMallocCoherent, pin = hipHostMallocDefault;
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.slots, S * sizeof(WorkerSlot), hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostMalloc((void **)&w.done, S * sizeof(uint64_t), hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipMalloc((void **)&w.fault, nblocks * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&w.brec, nblocks * 4u * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.srec, S * 4u * sizeof(uint32_t), hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostMalloc((void **)&w.next, nblocks * sizeof(uint64_t), hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostMalloc((void **)&w.ctl, sizeof(WorkerCtl), hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostMalloc((void **)&w.ptrs, S * M * 8u, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.lens, S * M * 2u, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.q, S * M * 2u, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.hash, S * M * 4u, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.qidx, S * M * 4u, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&w.qstart, S * w.qs_stride * 4u, hipHostMallocDefault)) !=
-            hipSuccess ||
-        (e = hipMalloc((void **)&w.win, (size_t)nblocks * M * YRSS_WIN_FULL)) != hipSuccess ||
-        (e = hipMalloc((void **)&w.len, (size_t)nblocks * M * 2u)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_slots, w.slots, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_done, w.done, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_srec, w.srec, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_next, w.next, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_ctl, w.ctl, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_ptrs, w.ptrs, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_lens, w.lens, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_q, w.q, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_hash, w.hash, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_qidx, w.qidx, 0)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&w.d_qstart, w.qstart, 0)) != hipSuccess) {
+        (e = w.slots.alloc(w.own, S, coh)) != hipSuccess ||
+        (e = w.done.alloc(w.own, S, coh)) != hipSuccess ||
+        (e = w.fault.alloc(w.own, B)) != hipSuccess ||
+        (e = w.brec.alloc(w.own, B * 4u)) != hipSuccess ||
+        (e = w.srec.alloc(w.own, S * 4u, coh)) != hipSuccess ||
+        (e = w.next.alloc(w.own, B, coh)) != hipSuccess ||
+        (e = w.ctl.alloc(w.own, 1, coh)) != hipSuccess ||
+        (e = w.ptrs.alloc(w.own, S * M, pin)) != hipSuccess ||
+        (e = w.lens.alloc(w.own, S * M, pin)) != hipSuccess ||
+        (e = w.q.alloc(w.own, S * M, pin)) != hipSuccess ||
+        (e = w.hash.alloc(w.own, S * M, pin)) != hipSuccess ||
+        (e = w.qidx.alloc(w.own, S * M, pin)) != hipSuccess ||
+        (e = w.qstart.alloc(w.own, S * w.qs_stride, pin)) != hipSuccess ||
+        (e = w.win.alloc(w.own, B * M * YRSS_WIN_FULL)) != hipSuccess ||
+        (e = w.len.alloc(w.own, B * M)) != hipSuccess) {
         worker_free(c);
         return hip_fail("yrss_worker_start", e);
     }
-    memset((void *)w.slots, 0, S * sizeof(WorkerSlot));
-    memset((void *)w.done, 0, S * sizeof(uint64_t));
-    memset((void *)w.srec, 0, S * 4u * sizeof(uint32_t));
+    memset((void *)w.slots.h, 0, S * sizeof(WorkerSlot));
+    memset((void *)w.done.h, 0, S * sizeof(uint64_t));
+    memset((void *)w.srec.h, 0, S * 4u * sizeof(uint32_t));
     for (uint32_t b = 0; b < nblocks; ++b)
-        w.next[b] = b + 1u;            // tickets start at 1; block b serves b+1, b+1+B, ...
-    memset((void *)w.ctl, 0, sizeof(WorkerCtl));
-    w.out = new yrss_ctx::WorkerState::Out[S];
-    w.last_out = new uint64_t[4 * S];
-    for (size_t i = 0; i < 4 * S; ++i)
-        w.last_out[i] = ~0ull;   // no previous burst: never "same"
-
-    for (size_t i = 0; i < S; ++i)
-        w.out[i] = yrss_ctx::WorkerState::Out{nullptr, nullptr, nullptr, nullptr, 0u, true, 0u};
+        w.next.h[b] = b + 1u;          // tickets start at 1; block b serves b+1, b+1+B, ...
+    memset((void *)w.ctl.h, 0, sizeof(WorkerCtl));
+    w.last_out.reset(new uint64_t[4 * S]);
+    std::fill_n(w.last_out.get(), 4 * S, ~0ull);   // no previous burst: never "same"
+    w.out.reset(new yrss_ctx::WorkerState::Out[S]);
+    std::fill_n(w.out.get(), S,
+                yrss_ctx::WorkerState::Out{nullptr, nullptr, nullptr, nullptr, 0u, true, 0u});
     w.issued = 0;
     w.on = true;
     return 0;
@@ -5338,23 +5330,23 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     const uint32_t si = (uint32_t)(t % w.nslots);
     if (!w.out[si].collected)
         return -EBUSY;   // the slot's previous ticket was not polled yet
-    WorkerSlot *sl = w.slots + si;
+    WorkerSlot *sl = w.slots.h + si;
     if (ptrs)
-        memcpy(w.ptrs + (size_t)si * kWorkerMaxBurst, ptrs, (size_t)n * 8u);
+        memcpy(w.ptrs.h + (size_t)si * kWorkerMaxBurst, ptrs, (size_t)n * 8u);
     sl->win = win;
     sl->stride = stride;
     if (lens)
-        memcpy(w.lens + (size_t)si * kWorkerMaxBurst, lens, (size_t)n * 2u);
+        memcpy(w.lens.h + (size_t)si * kWorkerMaxBurst, lens, (size_t)n * 2u);
     // Outputs the caller keeps in registered memory are written there by the
     // GPU (the poll copies nothing); others go through the slot's staging.
     const size_t base = (size_t)si * kWorkerMaxBurst;
     void *const user[4] = {out_q, out_hash, out_qidx, out_qstart};
     const size_t bytes[4] = {(size_t)n * 2u, (size_t)n * 4u, (size_t)n * 4u,
                              (w.nbk + 1u) * 4u};
-    void *const stage[4] = {w.d_q + base, w.d_hash + base, w.d_qidx + base,
-                            w.d_qstart + (size_t)si * w.qs_stride};
+    void *const stage[4] = {w.q.dh + base, w.hash.dh + base, w.qidx.dh + base,
+                            w.qstart.dh + (size_t)si * w.qs_stride};
     uint8_t copy = 0;
-    bool same = w.last_out != nullptr;
+    bool same = true;
     for (int k = 0; k < 4; ++k) {
         uint64_t d = 0;
         if (user[k]) {
@@ -5365,17 +5357,16 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
             }
         }
         sl->out[k] = d;
-        if (same && w.last_out[4 * si + k] != d)
+        if (w.last_out[4 * si + k] != d)
             same = false;
-        if (w.last_out)
-            w.last_out[4 * si + k] = d;
+        w.last_out[4 * si + k] = d;
     }
     sl->n = n;
     sl->flags = flags | (same ? kWorkerSameOut : 0u);
     w.out[si] = yrss_ctx::WorkerState::Out{out_q, out_hash, out_qidx, out_qstart, n, false, copy};
     ++w.pending;
     __atomic_store_n(&sl->seq, t, __ATOMIC_RELEASE);   // n and flags become visible first
-    __atomic_store_n(&w.ctl->pub, t, __ATOMIC_RELAXED);  // ring activity (idle is collective)
+    __atomic_store_n(&w.ctl.h->pub, t, __ATOMIC_RELAXED);  // ring activity (idle is collective)
     w.issued = t;
     *ticket = t;
     const int rc = worker_ensure(c);   // one cached load unless a workgroup left
@@ -5433,7 +5424,7 @@ int yrss_worker_poll(yrss_ctx *c, uint64_t ticket, int wait)
         return -EINVAL;
     auto &w = c->w;
     const uint32_t si = (uint32_t)(ticket % w.nslots);
-    const uint64_t *dn = w.done + si;
+    const uint64_t *dn = w.done.h + si;
     auto &o = w.out[si];
     if (ticket + w.nslots <= w.issued || o.collected)
         return -EINVAL;   // reused or already collected
@@ -5465,7 +5456,7 @@ int yrss_worker_poll(yrss_ctx *c, uint64_t ticket, int wait)
         // other burst in flight is blamed and nothing waits for the device):
         // logged, and kept in the context's record for yrss_fault_info when
         // that is empty
-        const uint32_t *g = w.srec + 4u * si;
+        const uint32_t *g = w.srec.h + 4u * si;
         fprintf(stderr, "yrss: device fault %u (%s) in %s at %u (value %u), worker ticket %llu; "
                         "per-queue lists invalid\n",
                 g[0], fault_name(g[0]), yrss_kernel_name((int)g[1]), g[2], g[3],
@@ -5476,7 +5467,7 @@ int yrss_worker_poll(yrss_ctx *c, uint64_t ticket, int wait)
         // writes the fields, so a record never mixes two faults.  (A reader
         // between the claim and the field stores sees the code with the
         // previous, cleared fields; take_fault reads after its own sync.)
-        uint32_t *r = c->d_fault_rec;
+        uint32_t *r = c->fault_rec.h;
         uint32_t expected = 0u;
         if (__atomic_compare_exchange_n(r, &expected, g[0], false, __ATOMIC_ACQ_REL,
                                         __ATOMIC_ACQUIRE)) {
@@ -5488,13 +5479,13 @@ int yrss_worker_poll(yrss_ctx *c, uint64_t ticket, int wait)
     }
     const size_t base = (size_t)si * kWorkerMaxBurst;
     if (o.copy & 1u)
-        memcpy(o.q, w.q + base, (size_t)o.n * 2u);
+        memcpy(o.q, w.q.h + base, (size_t)o.n * 2u);
     if (o.copy & 2u)
-        memcpy(o.hash, w.hash + base, (size_t)o.n * 4u);
+        memcpy(o.hash, w.hash.h + base, (size_t)o.n * 4u);
     if (o.copy & 4u)
-        memcpy(o.qidx, w.qidx + base, (size_t)o.n * 4u);
+        memcpy(o.qidx, w.qidx.h + base, (size_t)o.n * 4u);
     if (o.copy & 8u)
-        memcpy(o.qstart, w.qstart + (size_t)si * w.qs_stride, (w.nbk + 1u) * 4u);
+        memcpy(o.qstart, w.qstart.h + (size_t)si * w.qs_stride, (w.nbk + 1u) * 4u);
     return 0;
 }
 
@@ -5588,6 +5579,11 @@ int yrss_debug_partial_merge(yrss_ctx *c, int on)
         return -EINVAL;
     c->dbg.partial_merge = (uint32_t)on;
     return 0;
+}
+
+int64_t yrss_debug_live_buffers(void)
+{
+    return __atomic_load_n(&g_live_buffers, __ATOMIC_RELAXED);
 }
 
 #endif

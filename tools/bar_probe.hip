@@ -12,7 +12,8 @@
 // sees it and stores i into a completion word in pinned host memory, the
 // host spins on that.  Prints one JSON line: mode, round trip ns.
 // A mode whose memory the host cannot write dies with SIGSEGV (run each mode
-// as its own process).
+// as its own process).  No part of build(); built where it runs:
+//   hipcc --offload-arch=gfx950 -O2 tools/bar_probe.hip -o tools/bar_probe
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Build a library variant for same-box A/B runs (tools/gpu_ab_libs.sh,
-# tools/ab_seg.py): tools/build_ab_lib.sh NAME -DMACRO=V ...
+# Build a library variant for same-process A/B runs (a path leg of
+# tools/ab.py): tools/build_ab_lib.sh NAME -DMACRO=V ...
 #   -> ab/lib/libyrss_NAME.so
 # From the current tree, or from another checkout of the project named by
 # YRSS_AB_SRC (e.g. the parent commit exported with `git archive`).

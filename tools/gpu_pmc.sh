@@ -21,7 +21,7 @@ for np in $qs; do
     for pass in "$P1" "$P2" "$P3" "$P4"; do
         i=$((i + 1))
         d=gpurun_out/pmc_${tag}_q${np}_p$i
-        timeout -s KILL 120 rocprofv3 --pmc $pass -d $d -o run --output-format csv \
+        timeout -k 10 120 rocprofv3 --pmc $pass -d $d -o run --output-format csv \
             -- python bench.py $B > $d.log 2>&1 || { echo "pmc q$np pass $i rc=$?"; exit 1; }
     done
     echo "== q$np" >> "$out"

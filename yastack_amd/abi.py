@@ -307,7 +307,7 @@ def header_functions(path: Path = HEADER_PATH) -> list[str]:
 def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     """Load libyrss.so (once per path; default YRSS_LIB or the in-tree build).
     Raises YrssLibraryError if it is absent.  Distinct paths load side by side
-    (RTLD_LOCAL), which tools/ab_inproc.py uses to compare builds in one
+    (RTLD_LOCAL), which tools/ab.py uses to compare builds in one
     process."""
     global _lib
     if path is None and _lib is not None:

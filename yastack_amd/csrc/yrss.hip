@@ -992,7 +992,7 @@ __global__ __launch_bounds__(kScanBlock) void yrss_seg_scan(ScanParams P)
 // List stores are streaming and written through at device scope (nt | sc1):
 // with non-temporal stores alone the lines stayed dirty past the scatter and
 // their write-back landed in the next batch's parse kernel (+19 us there at 9
-// buckets, same-process A/B, profiles/r03_ab_inproc_store.log).
+// buckets, same-process A/B (tools/ab.py), profiles/r03_ab_inproc.log block 1).
 constexpr int kListAux = 18;   // nt | sc1
 // Past 64 buckets the line scatter's stores are non-temporal only: its
 // scatter ran 1.5-2.3 us (65 buckets) and 2.3-3.9 us (256) faster and the next

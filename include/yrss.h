@@ -546,7 +546,9 @@ int yrss_rss_check_dev(yrss_ctx *ctx, const struct yrss_rss_tuple *d_tuples, uin
 /* The whole ephemeral-port search of in_pcbconnect_setup (in_pcb.c:1131-1170)
  * in one launch: bit (p & 31) of bitmap[p >> 5] is ff_rss_check(faddr, laddr,
  * fport, p) for every stored (network-order) lport value p in 0..65535.
- * bitmap is 2048 host words.  Synchronous. */
+ * bitmap is 2048 host words.  Synchronous.  It runs through the host-burst
+ * staging, so while a YRSS_F_ASYNC burst is pending it returns -EBUSY, with
+ * bitmap untouched, until yrss_wait. */
 int yrss_rss_lport_sweep(yrss_ctx *ctx, uint32_t faddr, uint32_t laddr, uint16_t fport,
                          uint16_t nb_queues, uint16_t reta_size, uint16_t queueid,
                          uint32_t *bitmap);

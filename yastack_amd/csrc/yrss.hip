@@ -5114,9 +5114,13 @@ int yrss_rss_lport_sweep(yrss_ctx *c, uint32_t faddr, uint32_t laddr, uint16_t f
 {
     if (!c || !bitmap)
         return -EINVAL;
-    YRSS_HIP(hipSetDevice(c->device));
-    int rc = ensure_burst(c, 2048);
+    // the bitmap goes through the burst staging: not under a pending burst,
+    // whose kernel and copies own it (and ensure_burst may free it)
+    int rc = begin_burst(c);
     if (rc)
+        return rc;
+    YRSS_HIP(hipSetDevice(c->device));
+    if ((rc = ensure_burst(c, 2048)) != 0)
         return rc;
     RssCheckParams P;
     rss_check_params(c, nb_queues, reta_size, queueid, &P);

@@ -46,6 +46,18 @@ def ethertype_frame(ethertype: int, length: int = 64, pad_to: int = 80) -> bytes
     return bytes(b)
 
 
+def ipip_frame(inner_ihl, inner_proto, dport, outer_ihl=5, length=80):
+    b = bytearray(ipv4_frame("10.0.0.1", 1, "10.0.0.2", 2, proto=4, ihl=outer_ihl,
+                             length=length, ports_at_l4=False))
+    o = 14 + 4 * outer_ihl
+    b[o] = 0x40 | inner_ihl
+    b[o + 9] = inner_proto
+    p = o + 4 * inner_ihl
+    if inner_ihl >= 3 and p + 4 <= len(b):      # ports must not overwrite the header
+        struct.pack_into(">HH", b, p, 1111, dport)
+    return bytes(b)
+
+
 def tuple_82599(src: str, dst: str, sport: int, dport: int) -> bytes:
     """Network-order L3+L4 tuple as rte_softrss consumes it (test_thash.c)."""
     return socket.inet_aton(src) + socket.inet_aton(dst) + struct.pack(">HH", sport, dport)

@@ -20,13 +20,11 @@ import route_helpers as rh
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-import test_gpu_route_bursts as rb  # noqa: E402
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _check  # noqa: E402
+from gpu_checks import _gpu  # noqa: E402,F401
+from hostbufs import Out, check_lists, mbuf_pool, submit  # noqa: E402
 from yastack_amd import SoftRss, abi, segments  # noqa: E402
 
 POOL = 5000
-HEADROOM = 130
 CFG, NQ = (8, 8, 1, 0), 8
 # first allocation at the 1024 floor, a regrow, a regrow past the one-launch
 # limit (4096: the multi-launch path on the device twins), the one-launch path
@@ -35,33 +33,13 @@ STAGED = (32, 1500, 5000, 32)
 ZC = 1500
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-
-
-@functools.lru_cache(maxsize=None)
-def pool():
-    """(win uint8[POOL * 80], lens, frames, mbuf pool, mbuf ptrs, data ptrs)."""
-    win, lens = rh.stream(POOL)
-    lens = np.minimum(lens, 2048).astype(np.uint16)
-    frames = []
-    for i in range(POOL):
-        L = int(lens[i])
-        frames.append((win[i * 80:(i + 1) * 80].tobytes() + bytes(max(0, L - 80)))[:L])
-    mem, ptrs, _ = _fake_mbufs(frames, headroom=HEADROOM)
-    data = (ptrs + np.uint64(128 + HEADROOM)).astype(np.uint64)
-    lens.setflags(write=False)
-    return win, lens, frames, mem, ptrs, data
-
-
 @functools.lru_cache(maxsize=None)
 def expect(lo, n, stride=None):
     """The oracle's (q, hash, filter class, qidx, qstart) of pool packets
     [lo, lo + n) as one burst under KNI accept.  stride None: the host gather's
     rule (64-byte windows when every frame of the burst fits, else 80)."""
     from oracle import oracle
-    win, lens = pool()[:2]
+    win, lens = mbuf_pool(POOL)[:2]
     if stride is None:
         stride = 64 if int(lens[lo:lo + n].max()) <= 64 else 80
     w = np.ascontiguousarray(win.reshape(-1, 80)[lo:lo + n, :stride]).reshape(-1)
@@ -85,12 +63,12 @@ def _engine(lib_path=None):
 def staged_bursts(eng, after=lambda: None):
     """The staged bursts of STAGED and the zero-copy one on eng, each checked;
     after() runs once each burst size is done."""
-    frames, mem, ptrs = pool()[2], pool()[3], pool()[4]
+    frames, mem, ptrs = mbuf_pool(POOL).frames, mbuf_pool(POOL).mem, mbuf_pool(POOL).ptrs
     queue_id = 2
     for k, n in enumerate(STAGED):
         lo = _lo(n, k)
         q, h, f, qi, qs = expect(lo, n)
-        _check(eng.dispatch_frames(frames[lo:lo + n]), q, h, qi, qs)
+        check_lists(eng.dispatch_frames(frames[lo:lo + n]), q, h, qi, qs)
         if n <= 4096:
             r = eng.route_lists_frames(frames[lo:lo + n], queue_id)
             ri, rs = segments.route_lists_from(q, f, NQ, queue_id, True, True)
@@ -112,7 +90,7 @@ def staged_bursts(eng, after=lambda: None):
     eng.register_host_memory(mem.ctypes.data, mem.nbytes)
     lo = _lo(ZC, 5)
     q, h, _, qi, qs = expect(lo, ZC, 80)    # (the device gather always stages 80)
-    _check(eng.dispatch_burst_zc(ptrs[lo:lo + ZC]), q, h, qi, qs)
+    check_lists(eng.dispatch_burst_zc(ptrs[lo:lo + ZC]), q, h, qi, qs)
     eng.unregister_host_memory(mem.ctypes.data)
     assert eng.fault_info()[0] == abi.FAULT_NONE
     after()
@@ -125,7 +103,7 @@ WORKERS = ((8, 4, None, 3), (16, 2, 2, 3), (8, 4, None, 1))
 def worker_rounds(eng, around=lambda start_stop: start_stop()):
     """A plain worker, a route worker and a plain one again on eng, 32-packet
     bursts, each checked; around(f) runs f, one worker's start to its stop."""
-    lens, mem, ptrs, data = pool()[1], pool()[3], pool()[4], pool()[5]
+    _, lens, _, mem, ptrs, data = mbuf_pool(POOL)
     eng.register_host_memory(mem.ctypes.data, mem.nbytes)
     k = 0
     for nslots, nblocks, queue_id, bursts in WORKERS:
@@ -136,10 +114,10 @@ def worker_rounds(eng, around=lambda start_stop: start_stop()):
                 lo, k = _lo(32, 11 + k), k + 1
                 q, h, f, qi, qs = expect(lo, 32, 80)    # (the worker's gather stages 80)
                 if queue_id is None:
-                    _check(eng.worker_poll(eng.worker_submit(ptrs[lo:lo + 32])), q, h, qi, qs)
+                    check_lists(eng.worker_poll(eng.worker_submit(ptrs[lo:lo + 32])), q, h, qi, qs)
                 else:
-                    o = rb.Out(32, NQ, want_filter=False)
-                    t = rb._submit(eng, "mbufs", lo, 32, o, src=(lens, ptrs, data))
+                    o = Out(32, NQ, want_filter=False)
+                    t = submit(eng, "mbufs", lo, 32, o, (lens, ptrs, data))
                     assert eng._lib.yrss_worker_poll(eng._ctx, t, 1) == 0
                     o.check(q, h, f, queue_id, True, True)
             eng.worker_stop()

@@ -11,14 +11,8 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import FanOut  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _check, _expect, _frames  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
+from gpu_checks import dev  # noqa: E402,F401
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 
 @pytest.mark.parametrize("nctx,frames_form", [(2, False), (3, True), (1, False)])
@@ -27,11 +21,11 @@ def test_fanout_in_order_fifo(dev, oracle_mod, nctx, frames_form):
     rng = np.random.default_rng(nctx * 7 + frames_form)
     sizes = [32, 1024, 0, 1, 33] + [int(x) for x in rng.integers(0, 1025, 40)]
     total = sum(sizes)
-    frames = _frames(oracle_mod, total, 77 + nctx)
-    pool, ptrs, _ = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle_mod, total, 77 + nctx)
+    pool, ptrs, _ = fake_mbufs(frames, headroom=128)
     data = (ptrs + np.uint64(256)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
-    q_all, h_all, qi_all, qs_all = _expect(oracle_mod, frames, cfg)
+    q_all, h_all, qi_all, qs_all = expect_lists(oracle_mod, frames, cfg)
     nslots = 8
     with FanOut([0] * nctx, *cfg, nslots=nslots, nblocks=2) as fo:
         fo.register_host_memory(pool.ctypes.data, pool.nbytes)
@@ -55,7 +49,7 @@ def test_fanout_in_order_fifo(dev, oracle_mod, nctx, frames_form):
         for (t, r), f0, n in zip(got, firsts, sizes):
             q = q_all[f0:f0 + n]
             qi, qs = oracle_mod.process_burst(q, cfg[1])
-            _check(r, q, h_all[f0:f0 + n], qi, qs)
+            check_lists(r, q, h_all[f0:f0 + n], qi, qs)
             rq = np.asarray(r.qstart)
             for b in range(cfg[1] + 1):
                 lists[b].extend(int(f0) + int(x) for x in np.asarray(r.qidx)[rq[b]:rq[b + 1]])

@@ -15,14 +15,8 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs, run_and_compare  # noqa: E402
-from test_gpu_small_burst import _expect, _frames  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
+from gpu_checks import dev, run_and_compare  # noqa: E402,F401
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 
 def _cases(count, seed):
@@ -82,9 +76,9 @@ def test_random_large_batches(dev, oracle_mod, case):
 
 def test_two_threads_two_contexts(dev, oracle_mod):
     cfgs = [(3, 3, 1, 1), (8, 6, 1, 0)]
-    frames = _frames(oracle_mod, 6000, 77)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    expect = [_expect(oracle_mod, frames, c) for c in cfgs]
+    frames = synth_frames(oracle_mod, 6000, 77)
+    pool, ptrs, _ = fake_mbufs(frames)
+    expect = [expect_lists(oracle_mod, frames, c) for c in cfgs]
     errors = []
 
     def run(k):
@@ -99,10 +93,7 @@ def test_two_threads_two_contexts(dev, oracle_mod):
                          else eng.dispatch_burst(ptrs[off:off + n]))
                     q, h, _, _ = expect[k]
                     qi, qs = oracle_mod.process_burst(q[off:off + n], cfgs[k][1])
-                    assert np.array_equal(r.q, q[off:off + n])
-                    assert np.array_equal(r.hash, h[off:off + n])
-                    assert np.array_equal(r.qidx, qi)
-                    assert np.array_equal(r.qstart[: qs.size], qs)
+                    check_lists(r, q[off:off + n], h[off:off + n], qi, qs)
                 eng.unregister_host_memory(pool.ctypes.data)
         except BaseException as e:   # surfaced in the main thread
             errors.append((k, repr(e)))

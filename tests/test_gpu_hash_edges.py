@@ -19,16 +19,10 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import to_np  # noqa: E402
+from gpu_checks import dev, to_np  # noqa: E402,F401
 
 KEY2 = bytes(range(7, 47))
 N_DIRECTED = 300
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
 
 
 def _targets(d):

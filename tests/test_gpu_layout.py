@@ -24,63 +24,8 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_checks import check, dev, to_np  # noqa: E402,F401
 from yastack_amd import SoftRss, abi  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def to_np(t, dtype):
-    return t.cpu().numpy().view(dtype)
-
-
-KNI = ("accept", "0-32767", "1000-40000,53,123")
-
-
-def upload(traffic, dev):
-    """Host-built (win uint8, lens uint16) arrays as device tensors."""
-    win, lens = traffic
-    return (torch.from_numpy(np.ascontiguousarray(win)).to(dev),
-            torch.from_numpy(np.ascontiguousarray(lens).view(np.int16)).to(dev))
-
-
-def check(eng, oracle_mod, cfg_tuple, profile, n, stride=64, first=0, want_filter=False,
-          traffic=None, out=None):
-    """One device batch against the oracle: q, hash, qstart, qidx (and the
-    filter class when asked), plus an empty fault record.  traffic: host-built
-    (win, lens) instead of a synthetic profile; out: the caller's buffers."""
-    npr, nq, soft, only = cfg_tuple
-    if want_filter:
-        eng.set_kni(True, *KNI)
-    if traffic is None:
-        win, lens = eng.synth(profile, n, first, stride=stride)
-    else:
-        win, lens = upload(traffic, torch.device("cuda", 0))
-    res = eng.dispatch_dev(win, lens, stride, n, want_filter=want_filter, out=out)
-    torch.cuda.synchronize()
-    fault = eng.fault_info()
-    assert fault[0] == abi.FAULT_NONE, f"device guard fired: {fault}"
-    w_h = win[: n * stride].cpu().numpy()
-    l_h = to_np(lens[:n], np.uint16)
-    c = oracle_mod.cfg(npr, nq, soft, only)
-    q_ref, h_ref = oracle_mod.dispatch_windows(w_h, stride, l_h, c)
-    q = to_np(res.q[:n], np.int16)
-    h = to_np(res.hash[:n], np.uint32)
-    bad = np.nonzero((q != q_ref) | (h != h_ref))[0]
-    assert bad.size == 0, f"{bad.size} q/hash mismatches, first at {bad[:5]}"
-    qi_ref, qs_ref = oracle_mod.process_burst(q_ref, nq)
-    assert np.array_equal(to_np(res.qstart, np.uint32), qs_ref)
-    qi = to_np(res.qidx[:n], np.uint32)
-    d = np.nonzero(qi != qi_ref)[0]
-    assert d.size == 0, f"{d.size} qidx mismatches, first at {d[:5]}: {qi[d[:5]]} vs {qi_ref[d[:5]]}"
-    if want_filter:
-        want = oracle_mod.filter_windows(w_h, stride, l_h, True, oracle_mod.kni_bitmap(KNI[1]),
-                                         oracle_mod.kni_bitmap(KNI[2]))
-        assert np.array_equal(res.filter[:n].cpu().numpy(), want)
-    return res
 
 
 @pytest.mark.parametrize("want_filter", [False, True])

@@ -12,15 +12,10 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_checks import dev  # noqa: E402,F401
 from yastack_amd import SoftRss, abi  # noqa: E402
 
 CHUNK = 1 << 27
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
 
 
 def test_max_batch(dev, oracle_mod):

@@ -17,6 +17,8 @@ from frames import ethertype_frame, ipv4_frame
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_checks import dev, run_and_compare, to_np  # noqa: E402,F401
+from hostbufs import fake_mbufs, synth_frames  # noqa: E402
 from yastack_amd import SoftRss, abi  # noqa: E402
 
 CONFIGS = [
@@ -27,43 +29,6 @@ CONFIGS = [
     (4096, 256, 1, 1),
     (2, 3, 1, 1),     # nb_procs-1 == 1: hash % 1
 ]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def to_np(t, dtype):
-    return t.cpu().numpy().view(dtype)
-
-
-def run_and_compare(eng, oracle_mod, cfg_tuple, profile, n, stride, first=0, nflows=1 << 20,
-                    compact=True):
-    npr, nq, soft, only = cfg_tuple
-    win, lens = eng.synth(profile, n, first, nflows=nflows, stride=stride)
-    res = eng.dispatch_dev(win, lens, stride, n, compact=compact)
-    torch.cuda.synchronize()
-    w_h = win[: n * stride].cpu().numpy()
-    l_h = to_np(lens[:n], np.uint16)
-    # host generator produces the identical input
-    w_o, l_o = oracle_mod.synth(profile, min(n, 4096), first, nflows=nflows, stride=stride)
-    assert np.array_equal(w_h[: min(n, 4096) * stride], w_o)
-    assert np.array_equal(l_h[: min(n, 4096)], l_o)
-    c = oracle_mod.cfg(npr, nq, soft, only)
-    q_ref, h_ref = oracle_mod.dispatch_windows(w_h, stride, l_h, c)
-    q = to_np(res.q[:n], np.int16)
-    h = to_np(res.hash[:n], np.uint32)
-    bad = np.nonzero((q != q_ref) | (h != h_ref))[0]
-    assert bad.size == 0, f"{bad.size} mismatches, first at {bad[:5]}: q {q[bad[:5]]} vs " \
-                          f"{q_ref[bad[:5]]}, h {h[bad[:5]]} vs {h_ref[bad[:5]]}"
-    if compact:
-        qi_ref, qs_ref = oracle_mod.process_burst(q_ref, nq)
-        assert np.array_equal(to_np(res.qstart, np.uint32), qs_ref)
-        assert np.array_equal(to_np(res.qidx[:n], np.uint32), qi_ref)
-        assert eng.status() == 0
-    return q_ref, h_ref
 
 
 @pytest.mark.parametrize("cfg_tuple", CONFIGS)
@@ -188,35 +153,9 @@ def test_edge_frames_host_api(dev, oracle_mod):
         assert np.array_equal(r.qidx, qi_ref) and np.array_equal(r.qstart, qs_ref)
 
 
-def _fake_mbufs(frames, headroom=128):
-    """Lay frames out like an rte_mbuf pool: 128-B mbuf header + headroom + data.
-    The pool is page-aligned (hipHostRegister-able, like a hugepage memzone)."""
-    stride = 128 + headroom + 2048 + 64
-    raw = np.zeros(len(frames) * stride + 8192, np.uint8)
-    off = (-raw.ctypes.data) % 4096
-    pool = raw[off: off + len(frames) * stride]
-    base = pool.ctypes.data
-    ptrs = np.empty(len(frames), np.uint64)
-    for i, f in enumerate(frames):
-        m = i * stride
-        buf = base + m + 128
-        data = np.frombuffer(f[:2048], np.uint8)
-        pool[m + 128 + headroom: m + 128 + headroom + data.size] = data
-        pool[m: m + 8] = np.frombuffer(np.uint64(buf).tobytes(), np.uint8)       # buf_addr
-        pool[m + 16: m + 18] = np.frombuffer(np.uint16(headroom).tobytes(), np.uint8)  # data_off
-        pool[m + 40: m + 42] = np.frombuffer(np.uint16(min(len(f), 2048)).tobytes(), np.uint8)
-        ptrs[i] = base + m
-    return pool, ptrs, stride
-
-
 def test_burst_api_mbufs(dev, oracle_mod):
-    win, lens = oracle_mod.synth(abi.SYN_FUZZ, 3000, stride=80)
-    frames = []
-    for i in range(3000):
-        L = int(lens[i])
-        f = win[i * 80:(i + 1) * 80].tobytes()
-        frames.append((f + bytes(max(0, L - 80)))[:L] if L <= 2048 else f + bytes(2048 - 80))
-    pool, ptrs, stride = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, 3000, 0)
+    pool, ptrs, stride = fake_mbufs(frames)
     c = oracle_mod.cfg(3, 3, 1, 1)
     want = [oracle_mod.toeplitz_dispatch(f, len(f), c) for f in frames]
     with SoftRss(3, 3, 1, 1, device=0, max_burst=1024) as eng:   # grows past max_burst
@@ -333,13 +272,8 @@ def test_timing_hook(dev):
 def test_burst_zero_copy(dev, oracle_mod, headroom):
     """yrss_dispatch_burst_zc: the GPU reads rte_mbuf headers and data from
     registered host memory (any data alignment), writes hash.rss back."""
-    win, lens = oracle_mod.synth(abi.SYN_FUZZ, 5000, 11, stride=80)
-    frames = []
-    for i in range(5000):
-        L = int(lens[i])
-        f = win[i * 80:(i + 1) * 80].tobytes()
-        frames.append((f + bytes(max(0, L - 80)))[:L] if L <= 2048 else f + bytes(2048 - 80))
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=headroom)
+    frames = synth_frames(oracle_mod, 5000, 11)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=headroom)
     c = oracle_mod.cfg(5, 4, 1, 1)
     want = [oracle_mod.toeplitz_dispatch(f, len(f), c) for f in frames]
     with SoftRss(5, 4, 1, 1, device=0, max_burst=0) as eng:
@@ -361,13 +295,8 @@ def test_burst_zero_copy(dev, oracle_mod, headroom):
 
 def test_frames_zero_copy(dev, oracle_mod):
     """yrss_dispatch_frames_zc with arrays both staged and registered in place."""
-    win, lens = oracle_mod.synth(abi.SYN_FUZZ, 7000, 21, stride=80)
-    frames = []
-    for i in range(7000):
-        L = min(int(lens[i]), 2048)
-        f = win[i * 80:(i + 1) * 80].tobytes()
-        frames.append((f + bytes(max(0, L - 80)))[:L])
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=130)
+    frames = synth_frames(oracle_mod, 7000, 21)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=130)
     data = (ptrs + np.uint64(128 + 130)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
     c = oracle_mod.cfg(8, 8, 1, 0)

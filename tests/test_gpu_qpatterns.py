@@ -25,19 +25,12 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import qpatterns as qp  # noqa: E402
-from test_gpu_layout import check, to_np, upload  # noqa: E402
-from test_gpu_segments import check_seg  # noqa: E402
+from gpu_checks import check, check_seg, dev, to_np, upload  # noqa: E402,F401
+from hostbufs import PAD  # noqa: E402
 from yastack_amd import SoftRss, abi  # noqa: E402
 from yastack_amd.dispatch import DispatchResult  # noqa: E402
 
-PAD = 64          # spare elements behind every output, pre-filled
 _EX = {}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
 
 
 def ex_for(oracle_mod, cfg, stride):
@@ -126,7 +119,7 @@ def test_parse_without_lists(dev, oracle_mod, cfg):
         for name, pat in members(ex, n, chunk, span):
             bufs.refill()
             win_h, lens_h = qp.build(pat, ex)
-            win, lens = upload((win_h, lens_h), dev)
+            win, lens = upload(win_h, lens_h, dev)
             res = eng.dispatch_dev(win, lens, 64, n, out=bufs.out, compact=False)
             torch.cuda.synchronize()
             assert eng.fault_info()[0] == abi.FAULT_NONE, name

@@ -30,8 +30,7 @@ pytestmark = pytest.mark.gpu
 
 import qpatterns as qp  # noqa: E402
 import route_helpers as rh  # noqa: E402
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_route_bursts import HEADROOM, PAD, Arena, Out, _submit  # noqa: E402
+from hostbufs import PAD, Arena, Out, fake_mbufs, frames_of, submit  # noqa: E402
 from test_gpu_route_segments import check_route, upload  # noqa: E402
 from yastack_amd import SoftRss, abi, segments  # noqa: E402
 
@@ -88,6 +87,7 @@ def test_routed_segments(oracle_mod, kind, blocks, n):
 
 # ---- one-launch bursts -----------------------------------------------------------------
 
+HEADROOM = 130
 _MBUFS = {}
 
 
@@ -97,11 +97,8 @@ def mbufs_for(oracle_mod, kind):
     if kind not in _MBUFS:
         ex = qp.route_ex_for(oracle_mod, kind)
         used = np.unique(ex.table[ex.table >= 0])
-        frames = []
-        for i in used:
-            L = int(ex.lens[i])
-            frames.append((ex.win[i].tobytes() + bytes(max(0, L - ex.stride)))[:L])
-        mem, ptrs, _ = _fake_mbufs(frames, headroom=HEADROOM)
+        frames = frames_of(ex.win[used].reshape(-1), ex.lens[used], ex.stride)
+        mem, ptrs, _ = fake_mbufs(frames, headroom=HEADROOM)
         mp = np.zeros(ex.lens.size, np.uint64)
         mp[used] = ptrs
         dp = np.zeros(ex.lens.size, np.uint64)
@@ -201,7 +198,7 @@ def test_route_worker(oracle_mod, kind, n):
                     wreg = SimpleNamespace(mem=stage.take(n * 80, np.uint8, 0))
                     if form == "windows":
                         wreg.mem[:] = np.ascontiguousarray(ex.win[qp.choose(pat, ex)]).reshape(-1)
-                    t = _submit(eng, form, 0, n, o, wreg, src=(lens, mp, dp))
+                    t = submit(eng, form, 0, n, o, (lens, mp, dp), wreg)
                     flight.append((t, name, o, q, h, f, (lens, mp, dp, wreg)))
                 for t, name, o, q, h, f, _keep in flight:
                     assert eng._lib.yrss_worker_poll(eng._ctx, t, 1) == 0, name

@@ -12,23 +12,18 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_small_burst import _expect, _frames  # noqa: E402
+from gpu_checks import dev  # noqa: E402,F401
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 DISPATCH_FUNC_T = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint16,
                                    ctypes.c_uint16, ctypes.c_uint16)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
-
-
 @pytest.mark.parametrize("cfg", [(3, 3, 1, 1), (5, 4, 1, 0), (4, 2, 0, 1)])
 def test_registered_dispatcher_matches_oracle(dev, oracle_mod, cfg):
     lib = abi.load()
-    frames = _frames(oracle_mod, 300, 500 + cfg[0])
-    q, _, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, 300, 500 + cfg[0])
+    q, _, _, _ = expect_lists(oracle_mod, frames, cfg)
     fn = DISPATCH_FUNC_T(ctypes.cast(lib.yrss_toeplitz_dispatch, ctypes.c_void_p).value)
     with SoftRss(*cfg, device=0) as eng:
         assert lib.yrss_set_dispatch_ctx(eng._ctx) == 0
@@ -45,10 +40,9 @@ def test_registered_dispatcher_matches_oracle(dev, oracle_mod, cfg):
 def test_python_wrappers(dev, oracle_mod):
     """SoftRss.toeplitz_dispatch and SoftRss.worker_submit_frames."""
     cfg = (3, 3, 1, 1)
-    frames = _frames(oracle_mod, 200, 606)
-    q, h, _, _ = _expect(oracle_mod, frames, cfg)
-    from test_gpu_parity import _fake_mbufs
-    pool, ptrs, _ = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle_mod, 200, 606)
+    q, h, _, _ = expect_lists(oracle_mod, frames, cfg)
+    pool, ptrs, _ = fake_mbufs(frames, headroom=128)
     data = (ptrs + np.uint64(128 + 128)).astype(np.uint64)
     lens = np.array([len(f) for f in frames], np.uint16)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
@@ -60,8 +54,7 @@ def test_python_wrappers(dev, oracle_mod):
             r = eng.worker_poll(t)
             sl = slice(50 * k, 50 * k + 50)
             qi, qs = oracle_mod.process_burst(q[sl], cfg[1])
-            assert np.array_equal(r.q, q[sl]) and np.array_equal(r.hash, h[sl])
-            assert np.array_equal(r.qidx, qi) and np.array_equal(r.qstart[: qs.size], qs)
+            check_lists(r, q[sl], h[sl], qi, qs)
         eng.worker_stop()
         eng.unregister_host_memory(pool.ctypes.data)
 
@@ -73,8 +66,8 @@ def test_registered_dispatcher_through_worker(dev, oracle_mod, cfg):
     copies each window into its own registered slot), lengths past the
     80-byte window included."""
     lib = abi.load()
-    frames = _frames(oracle_mod, 300, 700 + cfg[0])
-    q, _, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, 300, 700 + cfg[0])
+    q, _, _, _ = expect_lists(oracle_mod, frames, cfg)
     fn = DISPATCH_FUNC_T(ctypes.cast(lib.yrss_toeplitz_dispatch, ctypes.c_void_p).value)
     with SoftRss(*cfg, device=0) as eng:
         eng.worker_start(4, 1)

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 from yastack_amd import abi  # noqa: E402
 from yastack_amd.remote import RemoteRss  # noqa: E402
 
-from test_gpu_small_burst import _expect, _frames  # noqa: E402
+from hostbufs import expect_lists, synth_frames  # noqa: E402
 
 
 def _cfg(npr, nq, soft, only):
@@ -30,14 +30,14 @@ def _cfg(npr, nq, soft, only):
 def _check(oracle_mod, frames, cfg, res):
     rc, q, h, qi, qs = res
     assert rc == 0
-    qr, hr, qir, qsr = _expect(oracle_mod, frames, cfg)
+    qr, hr, qir, qsr = expect_lists(oracle_mod, frames, cfg)
     assert np.array_equal(q, qr) and np.array_equal(h, hr)
     assert np.array_equal(qi, qir) and np.array_equal(qs[: qsr.size], qsr)
 
 
 @pytest.mark.parametrize("cfg", [(3, 3, 1, 1), (8, 8, 1, 0)])
 def test_remote_bursts_bit_exact(oracle_mod, cfg):
-    frames = _frames(oracle_mod, 2000, 31 + cfg[0])
+    frames = synth_frames(oracle_mod, 2000, 31 + cfg[0])
     sizes = [32, 1, 1024, 300, 0, 643]
     with RemoteRss(_cfg(*cfg), nslots=8, max_burst=1024, nblocks=4, timeout_ms=20000) as r:
         off, tk = 0, []
@@ -50,7 +50,7 @@ def test_remote_bursts_bit_exact(oracle_mod, cfg):
 
 def test_remote_helper_killed_then_restarted(oracle_mod):
     cfg = (5, 4, 1, 1)
-    frames = _frames(oracle_mod, 640, 77)
+    frames = synth_frames(oracle_mod, 640, 77)
     with RemoteRss(_cfg(*cfg), nslots=16, max_burst=64, nblocks=4, timeout_ms=20000) as r:
         first = r.submit(frames[:64])
         _check(oracle_mod, frames[:64], cfg, r.poll(first))

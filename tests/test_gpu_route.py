@@ -6,14 +6,14 @@ import struct
 import numpy as np
 import pytest
 
-from frames import ipv4_frame
+from frames import ipip_frame, ipv4_frame
 from route_helpers import Rings
-from test_gpu_parity import _fake_mbufs, to_np
-from test_kni_oracle import ipip_frame
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_checks import to_np  # noqa: E402
+from hostbufs import fake_mbufs, synth_frames  # noqa: E402
 from yastack_amd import SoftRss, abi  # noqa: E402
 
 KNI_CFGS = [
@@ -94,25 +94,14 @@ def test_set_kni_rejects_bad_method():
         eng.set_kni(False, None, None, None)
 
 
-def _fuzz_frames(oracle_mod, n):
-    """The SYN_FUZZ stream as frames of their stated length (at most 2048 bytes)."""
-    win, lens = oracle_mod.synth(abi.SYN_FUZZ, n, 5, stride=80)
-    frames = []
-    for i in range(n):
-        L = min(int(lens[i]), 2048)
-        f = win[i * 80:(i + 1) * 80].tobytes()
-        frames.append((f + bytes(max(0, L - 80)))[:L])
-    return frames
-
-
 @pytest.mark.parametrize("queue_id", [0, 1])
 @pytest.mark.parametrize("kni", [(False, "reject"), (True, "accept"), (True, "reject")])
 @pytest.mark.parametrize("cap", [10**6, 300])
 @pytest.mark.parametrize("n", [3000, 6000])   # one-launch small path / multi-kernel path
 def test_route_burst_vs_process_packets(oracle_mod, queue_id, kni, cap, n):
     nq = 4
-    frames = _fuzz_frames(oracle_mod, n)
-    pool, ptrs, stride = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, n, 5)
+    pool, ptrs, stride = fake_mbufs(frames)
     addr_to_idx = {int(a): i for i, a in enumerate(ptrs)}
     clone_ok = lambda i, j: (i * 7 + j) % 5 != 0          # noqa: E731 — some clones fail
     capacity = [cap] * nq
@@ -146,8 +135,8 @@ def test_route_burst_above_route_lists_cap(oracle_mod, queue_id, method):
     bucket limit, not the hand-off's): 600 packets, one launch over two full
     and one partial 256-packet chunk; ring 2 (350 packets for 300 slots) fills."""
     nq, n, cap = 70, 600, 300
-    frames = _fuzz_frames(oracle_mod, n)
-    pool, ptrs, stride = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, n, 5)
+    pool, ptrs, stride = fake_mbufs(frames)
     addr_to_idx = {int(a): i for i, a in enumerate(ptrs)}
     clone_ok = lambda i, j: (i * 7 + j) % 5 != 0          # noqa: E731 — some clones fail
     tcp_ports, udp_ports = "0-30000", "20000-65535"

@@ -9,7 +9,6 @@ its end; every test ends with yrss_fault_info clean.  Input: the first POOL
 packets of route_helpers.stream (oracle.synth SYN_FUZZ from packet 5), laid out
 once as an rte_mbuf pool; a burst is a slice of it.  data_len is capped at
 2048 (one mbuf segment), and the oracle sees the capped lengths."""
-import ctypes
 import errno
 import functools
 
@@ -22,38 +21,16 @@ import route_lists_helpers as rl
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from frames import ethertype_frame, ipv4_frame  # noqa: E402
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_kni_oracle import ipip_frame  # noqa: E402
+from frames import ethertype_frame, ipip_frame, ipv4_frame  # noqa: E402
+from gpu_checks import _gpu  # noqa: E402,F401
+from hostbufs import PAD, Arena, Out, fake_mbufs, mbuf_pool, submit  # noqa: E402
 from yastack_amd import SoftRss, abi, segments  # noqa: E402
 
 POOL = 4200
-PAD = 64
-HEADROOM = 130
 # nb_queues -> (nb_procs, nb_queues, soft_dispatch, dispatch_only_core); the route
 # bucket counts are 4, 6, 16, 17 (one more ballot bit in peer_mask) and 64 (the cap)
 CFG = {1: (4, 1, 1, 0), 3: (3, 3, 1, 0), 13: (13, 13, 1, 0), 14: (14, 14, 1, 0),
        61: (61, 61, 1, 0)}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-
-
-@functools.lru_cache(maxsize=None)
-def pool():
-    """(win uint8[POOL * 80], lens uint16[POOL], mbuf pool, mbuf ptrs, data ptrs)."""
-    win, lens = rh.stream(POOL)
-    lens = np.minimum(lens, 2048).astype(np.uint16)
-    frames = []
-    for i in range(POOL):
-        L = int(lens[i])
-        frames.append((win[i * 80:(i + 1) * 80].tobytes() + bytes(max(0, L - 80)))[:L])
-    mem, ptrs, _ = _fake_mbufs(frames, headroom=HEADROOM)
-    data = (ptrs + np.uint64(128 + HEADROOM)).astype(np.uint64)
-    lens.setflags(write=False)
-    return win, lens, mem, ptrs, data
 
 
 @functools.lru_cache(maxsize=None)
@@ -65,7 +42,7 @@ def _kni_bitmaps():
 @functools.lru_cache(maxsize=None)
 def _full(cfg, enable):
     from oracle import oracle
-    win, lens = pool()[:2]
+    win, lens = mbuf_pool(POOL)[:2]
     q, h = oracle.dispatch_windows(win, 80, lens, oracle.cfg(*cfg))
     return q, h, oracle.filter_windows(win, 80, lens, enable, *_kni_bitmaps())
 
@@ -75,7 +52,7 @@ def expect(cfg, enable, lo, n, stride=None):
     burst.  stride None: the host gather's rule (64-byte windows when every
     frame of the burst fits, else 80); the worker's gather always stages 80."""
     from oracle import oracle
-    win, lens = pool()[:2]
+    win, lens = mbuf_pool(POOL)[:2]
     if stride is None:
         stride = 64 if n and int(lens[lo:lo + n].max()) <= 64 else 80
     if stride == 80 or n == 0:
@@ -86,72 +63,8 @@ def expect(cfg, enable, lo, n, stride=None):
     return q, h, oracle.filter_windows(w, stride, ln, enable, *_kni_bitmaps())
 
 
-class Out:
-    """Output arrays longer than the burst, pre-filled; in `arena` (registered
-    memory) when given."""
-
-    def __init__(self, n, nq, want_hash=True, want_filter=True, arena=None):
-        def arr(count, dtype, fill):
-            if arena is None:
-                return np.full(count, fill, dtype)
-            return arena.take(count, dtype, fill)
-        self.n, self.nq = n, nq
-        self.q = arr(n + PAD, np.int16, 0x5A5A)
-        self.h = arr(n + PAD, np.uint32, 0x5A5A5A5A) if want_hash else None
-        self.f = np.full(n + PAD, 0x5A, np.int8) if want_filter else None
-        self.ri = arr(n + PAD, np.uint32, 0xEEEEEEEE)
-        self.rs = arr(nq + 4 + PAD, np.uint32, 0x77777777)
-
-    @staticmethod
-    def p(a):
-        return None if a is None else a.ctypes.data
-
-    def check(self, q, h, f, queue_id, enable, accept, filter_written=True):
-        n, nq = self.n, self.nq
-        assert np.array_equal(self.q[:n], q) and np.all(self.q[n:] == 0x5A5A)
-        if self.h is not None:
-            assert np.array_equal(self.h[:n], h) and np.all(self.h[n:] == 0x5A5A5A5A)
-        if self.f is not None:
-            if filter_written:
-                assert np.array_equal(self.f[:n], f)
-                assert np.all(self.f[n:] == 0x5A)
-            else:
-                assert np.all(self.f == 0x5A)
-        ri_ref, rs_ref = segments.route_lists_from(q, f, nq, queue_id, enable, accept)
-        assert np.array_equal(self.rs[:nq + 4], rs_ref), (self.rs[:nq + 4], rs_ref)
-        assert np.all(self.rs[nq + 4:] == 0x77777777)
-        d = np.nonzero(self.ri[:n] != ri_ref)[0]
-        assert d.size == 0, f"{d.size} ridx mismatches, first at {d[:5]}: {self.ri[d[:5]]} vs " \
-                            f"{ri_ref[d[:5]]}"
-        assert np.all(self.ri[n:] == 0xEEEEEEEE)
-
-    def untouched(self):
-        return (np.all(self.q == 0x5A5A) and np.all(self.ri == 0xEEEEEEEE) and
-                np.all(self.rs == 0x77777777) and (self.h is None or np.all(self.h == 0x5A5A5A5A))
-                and (self.f is None or np.all(self.f == 0x5A)))
-
-
-class Arena:
-    """A page-aligned stretch of host memory to register, handed out in
-    64-byte-aligned pieces."""
-
-    def __init__(self, nbytes):
-        raw = np.zeros(nbytes + 8192, np.uint8)
-        off = (-raw.ctypes.data) % 4096
-        self.mem = raw[off:off + (nbytes + 4095) // 4096 * 4096]
-        self.used = 0
-
-    def take(self, count, dtype, fill):
-        nbytes = count * np.dtype(dtype).itemsize
-        a = self.mem[self.used:self.used + nbytes].view(dtype)
-        assert a.size == count, "arena exhausted"
-        self.used += (nbytes + 63) // 64 * 64
-        a[:] = fill
-        return a
-
-
 def one_launch(eng, form, lo, n, queue_id, want_hash=True, want_filter=True, flags=0):
-    _, lens, _, ptrs, data = pool()
+    _, lens, _, _, ptrs, data = mbuf_pool(POOL)
     o = Out(n, eng.nb_queues, want_hash, want_filter)
     if form == "mbufs":
         rc = eng._lib.yrss_route_lists_burst(eng._ctx, ptrs[lo:].ctypes.data, n, queue_id,
@@ -202,7 +115,7 @@ def test_one_launch_routes(oracle_mod, nq, kni):
 
 def test_one_launch_write_rss_and_empty_burst(oracle_mod):
     cfg, nq, n, lo = CFG[3], 3, 300, 100
-    mem, ptrs = pool()[2], pool()[3]
+    mem, ptrs = mbuf_pool(POOL).mem, mbuf_pool(POOL).ptrs
     stride = int(ptrs[1] - ptrs[0])
     rows = mem.reshape(-1, stride)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
@@ -300,7 +213,7 @@ def test_directed_bursts(oracle_mod, name):
     q, h, f = _expect_frames(oracle_mod, frames, cfg, enable, tcp, udp)
     bkt = segments.route_buckets(q, f, nq, queue_id, enable, accept)
     assert [int(b) for b in bkt] == [want_class(i, n, nq) for i in range(n)]
-    mem, ptrs, _ = _fake_mbufs(frames, headroom=128)
+    mem, ptrs, _ = fake_mbufs(frames, headroom=128)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.set_kni(enable, method, tcp, udp)
         ri_ref, rs_ref = segments.route_lists_from(q, f, nq, queue_id, enable, accept)
@@ -342,31 +255,10 @@ BURSTS = [1, 32, 0, 63, 64, 65, 1000, 1024]
 
 
 def _registered_windows():
-    win = pool()[0]
+    win = mbuf_pool(POOL).win
     a = Arena(win.size)
     a.mem[:win.size] = win
     return a
-
-
-def _submit(eng, form, lo, n, o, wreg=None, stride=80, write_rss=False, src=None):
-    """src: (lens, mbuf ptrs, frame data ptrs) to slice in place of pool()'s."""
-    lens, ptrs, data = src if src is not None else (pool()[1], pool()[3], pool()[4])
-    t = ctypes.c_uint64()
-    lib, ctx = eng._lib, eng._ctx
-    if form == "mbufs":
-        rc = lib.yrss_worker_submit(ctx, ptrs[lo:].ctypes.data, n, o.p(o.q), o.p(o.h), o.p(o.ri),
-                                    o.p(o.rs), abi.F_WRITE_RSS if write_rss else 0,
-                                    ctypes.byref(t))
-    elif form == "frames":
-        rc = lib.yrss_worker_submit_frames(ctx, data[lo:].ctypes.data, lens[lo:].ctypes.data, n,
-                                           o.p(o.q), o.p(o.h), o.p(o.ri), o.p(o.rs),
-                                           ctypes.byref(t))
-    else:
-        rc = lib.yrss_worker_submit_windows(ctx, wreg.mem[lo * 80:].ctypes.data, stride,
-                                            lens[lo:].ctypes.data, n, o.p(o.q), o.p(o.h),
-                                            o.p(o.ri), o.p(o.rs), ctypes.byref(t))
-    assert rc == 0, (form, n, rc)
-    return t.value
 
 
 @pytest.mark.parametrize("nslots,nblocks,nq,queue_id", [
@@ -376,7 +268,8 @@ def test_route_worker_bursts(oracle_mod, nslots, nblocks, nq, queue_id):
     submit forms, YRSS_F_WRITE_RSS on the mbufs form, outputs in registered
     memory and in slot staging, hash wanted and not."""
     cfg = CFG[nq]
-    mem, ptrs = pool()[2], pool()[3]
+    _, lens, _, mem, ptrs, data = mbuf_pool(POOL)
+    src = (lens, ptrs, data)
     rows = mem.reshape(-1, int(ptrs[1] - ptrs[0]))
     rows[:, 44:48] = 0
     sizes = BURSTS * 2 if nslots == 8 else BURSTS + BURSTS[:nslots]
@@ -398,7 +291,8 @@ def test_route_worker_bursts(oracle_mod, nslots, nblocks, nq, queue_id):
                 o = Out(n, nq, want_hash=k % 4 != 3, want_filter=False,
                         arena=arena if k % 2 else None)
                 write_rss = form == "mbufs" and k % 2 == 0
-                flight.append((_submit(eng, form, lo, n, o, wreg, write_rss=write_rss), lo, n, o))
+                flight.append((submit(eng, form, lo, n, o, src, wreg, write_rss=write_rss), lo, n,
+                               o))
                 if write_rss:
                     wb.append((lo, n))
             for t, lo, n, o in flight:
@@ -451,7 +345,7 @@ def test_set_kni_on_a_route_worker_and_a_plain_worker_alongside(oracle_mod):
     is pending; a plain worker on a second context keeps giving the global
     per-queue lists."""
     cfg, nq, queue_id, n = CFG[3], 3, 2, 500
-    mem, ptrs = pool()[2], pool()[3]
+    _, lens, _, mem, ptrs, data = mbuf_pool(POOL)
     lists = []
     with SoftRss(*cfg, device=0, max_burst=0) as eng, \
             SoftRss(*cfg, device=0, max_burst=0) as plain:
@@ -464,7 +358,7 @@ def test_set_kni_on_a_route_worker_and_a_plain_worker_alongside(oracle_mod):
             eng.set_kni(enable, method, rh.TCP_PORTS, rh.UDP_PORTS)
             lo = lo_for(n, 50)
             o = Out(n, nq, want_filter=False)
-            t = _submit(eng, "mbufs", lo, n, o)
+            t = submit(eng, "mbufs", lo, n, o, (lens, ptrs, data))
             tp = plain.worker_submit(ptrs[lo:lo + n])
             if k == 1:      # a burst is pending: the state it runs under stays
                 rc = eng._lib.yrss_set_kni(eng._ctx, 0, b"reject", None, None)
@@ -494,7 +388,7 @@ def test_end_to_end_hand_off(oracle_mod, queue_id):
     limited capacity and failing clones: the per-packet model's result, ring
     order the reference's one-at-a-time order."""
     cfg, nq = (6, 4, 1, 0), 4
-    mem, ptrs = pool()[2], pool()[3]
+    mem, ptrs = mbuf_pool(POOL).mem, mbuf_pool(POOL).ptrs
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.set_kni(True, "accept", rh.TCP_PORTS, rh.UDP_PORTS)
         eng.register_host_memory(mem.ctypes.data, mem.nbytes)

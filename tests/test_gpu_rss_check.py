@@ -15,8 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _check, _expect, _frames  # noqa: E402
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 CFGS = [(1, 128, 0), (2, 128, 1), (3, 512, 2), (8, 128, 5), (4, 0, 3), (5, 64, 0)]
 
@@ -407,15 +406,15 @@ def test_lport_sweep_between_bursts(oracle_mod):
     nq, reta, qid = 4, 128, 1
     want, _, _ = _sweep_want(oracle_mod, faddr, laddr, fport, nq, reta, qid)
     assert not _uniform(want)
-    f1 = _frames(oracle_mod, 1000, 31)
-    f2 = _frames(oracle_mod, 3000, 32)
-    pool, ptrs, _ = _fake_mbufs(f2)
+    f1 = synth_frames(oracle_mod, 1000, 31)
+    f2 = synth_frames(oracle_mod, 3000, 32)
+    pool, ptrs, _ = fake_mbufs(f2)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         first = eng.rss_lport_sweep(faddr, laddr, fport, nq, reta, qid)
         assert np.array_equal(first, want)
-        _check(eng.dispatch_frames(f1), *_expect(oracle_mod, f1, cfg))
+        check_lists(eng.dispatch_frames(f1), *expect_lists(oracle_mod, f1, cfg))
         assert np.array_equal(eng.rss_lport_sweep(faddr, laddr, fport, nq, reta, qid), first)
-        _check(eng.dispatch_burst(ptrs), *_expect(oracle_mod, f2, cfg))
+        check_lists(eng.dispatch_burst(ptrs), *expect_lists(oracle_mod, f2, cfg))
         assert np.array_equal(eng.rss_lport_sweep(faddr, laddr, fport, nq, reta, qid), first)
         assert eng.status() == 0
     del pool
@@ -432,9 +431,9 @@ def test_lport_sweep_refused_mid_burst(oracle_mod):
     faddr, laddr, fport = _EXISTING
     nq, reta, qid = 4, 128, 1
     want, _, _ = _sweep_want(oracle_mod, faddr, laddr, fport, nq, reta, qid)
-    frames = _frames(oracle_mod, n, 41)
-    q, h, qi, qs = _expect(oracle_mod, frames, cfg)
-    pool, ptrs, _ = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, n, 41)
+    q, h, qi, qs = expect_lists(oracle_mod, frames, cfg)
+    pool, ptrs, _ = fake_mbufs(frames)
     lib = abi.load()
     oq, oh = np.empty(n, np.int16), np.empty(n, np.uint32)
     oqi, oqs = np.empty(n, np.uint32), np.empty(cfg[1] + 2, np.uint32)

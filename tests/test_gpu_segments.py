@@ -18,73 +18,8 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_checks import SEG_KNI, check_seg, padded_seg_out, to_np  # noqa: E402
 from yastack_amd import SoftRss, abi, segments  # noqa: E402
-from yastack_amd.dispatch import SegResult  # noqa: E402
-
-PAD = 64          # spare elements behind every output, pre-filled
-KNI = ("accept", "80", "53")
-
-
-def to_np(t, dtype):
-    return t.cpu().numpy().view(dtype)
-
-
-def padded_out(eng, n, dev, want_filter=False):
-    nseg = segments.nseg_for(n)
-    return SegResult(
-        q=torch.full((n + PAD,), 0x5A5A, dtype=torch.int16, device=dev),
-        hash=torch.full((n + PAD,), 0x5A5A5A5A, dtype=torch.int32, device=dev),
-        filter=torch.full((n + PAD,), 0x5A, dtype=torch.int8, device=dev) if want_filter else None,
-        seg_idx=torch.full((n + PAD,), 0xEE, dtype=torch.uint8, device=dev),
-        seg_off=torch.full((nseg + 1, eng.nb_queues + 2), 0x7777, dtype=torch.int16, device=dev))
-
-
-def check_seg(eng, oracle_mod, cfg, profile, n, stride=64, first=0, want_filter=False,
-              traffic=None):
-    """One segmented batch against the oracle; returns (result, q_ref).
-    traffic: host-built (win uint8, lens uint16) instead of a synthetic profile."""
-    npr, nq, soft, only = cfg
-    dev = torch.device("cuda", 0)
-    if traffic is None:
-        win, lens = eng.synth(profile, n, first, stride=stride)
-    else:
-        win = torch.from_numpy(np.ascontiguousarray(traffic[0])).to(dev)
-        lens = torch.from_numpy(np.ascontiguousarray(traffic[1]).view(np.int16)).to(dev)
-    out = padded_out(eng, n, dev, want_filter)
-    res = eng.dispatch_dev_seg(win, lens, stride, n, out=out)
-    torch.cuda.synchronize()
-    assert eng.status() == 0
-    w_h = win[: n * stride].cpu().numpy()
-    l_h = to_np(lens[:n], np.uint16)
-    q_ref, h_ref = oracle_mod.dispatch_windows(w_h, stride, l_h, oracle_mod.cfg(npr, nq, soft, only))
-    q = to_np(res.q, np.int16)
-    h = to_np(res.hash, np.uint32)
-    bad = np.nonzero((q[:n] != q_ref) | (h[:n] != h_ref))[0]
-    assert bad.size == 0, f"{bad.size} q/hash mismatches, first at {bad[:5]}"
-    si_ref, so_ref = segments.from_q(q_ref, nq)
-    nseg = segments.nseg_for(n)
-    so = to_np(res.seg_off, np.uint16)
-    si = res.seg_idx.cpu().numpy()
-    rows = np.nonzero((so[:nseg] != so_ref).any(axis=1))[0]
-    assert rows.size == 0, f"seg_off differs in {rows.size} segments, first {rows[:3]}: " \
-                           f"{so[rows[:1]]} vs {so_ref[rows[:1]]}"
-    d = np.nonzero(si[:n] != si_ref)[0]
-    assert d.size == 0, f"{d.size} seg_idx mismatches, first at {d[:5]}: {si[d[:5]]} vs " \
-                        f"{si_ref[d[:5]]}"
-    # nothing past the batch's end
-    assert np.all(q[n:] == 0x5A5A) and np.all(h[n:] == 0x5A5A5A5A)
-    assert np.all(si[n:] == 0xEE) and np.all(so[nseg] == 0x7777)
-    if want_filter:
-        want = oracle_mod.filter_windows(w_h, stride, l_h, True, oracle_mod.kni_bitmap(KNI[1]),
-                                         oracle_mod.kni_bitmap(KNI[2]))
-        f = res.filter.cpu().numpy()
-        assert np.array_equal(f[:n], want)
-        assert np.all(f[n:] == 0x5A)
-    # the accessor: segment 0's buckets are the expected slices
-    for b in range(nq + 1):
-        assert np.array_equal(res.segment(0, b).cpu().numpy(),
-                              si_ref[int(so_ref[0, b]):int(so_ref[0, b + 1])])
-    return res, q_ref
 
 
 @pytest.mark.parametrize("stride", [64, 80])
@@ -134,7 +69,7 @@ def test_chunk_tiles_tuning_does_not_apply(oracle_mod):
 def test_filter_on(oracle_mod, n):
     cfg = (8, 8, 1, 0)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
-        eng.set_kni(True, *KNI)
+        eng.set_kni(True, *SEG_KNI)
         for profile in (abi.SYN_FUZZ, abi.SYN_IMIX):
             check_seg(eng, oracle_mod, cfg, profile, n, stride=80, first=17, want_filter=True)
 
@@ -183,7 +118,7 @@ def test_refusals_before_any_launch():
     with SoftRss(8, 8, 1, 0, device=0, max_burst=0) as eng:
         n = 300
         win, lens = eng.synth(abi.SYN_TCP4, n)
-        out = padded_out(eng, n, dev)
+        out = padded_seg_out(eng, n, dev, want_filter=False)
 
         def call(n_arg, seg_idx_ptr, seg_off_ptr=None):
             b = abi.DevSegBatch(win.data_ptr(), 64, n_arg, lens.data_ptr(), out.q.data_ptr(),
@@ -203,6 +138,6 @@ def test_refusals_before_any_launch():
         assert np.all(out.seg_idx.cpu().numpy() == 0xEE)
         assert np.all(to_np(out.q, np.uint16) == 0x5A5A)
         with pytest.raises(ValueError, match="seg_idx"):
-            small = padded_out(eng, n, dev)
+            small = padded_seg_out(eng, n, dev, want_filter=False)
             small.seg_idx = small.seg_idx[: n - 1]
             eng.dispatch_dev_seg(win, lens, 64, n, out=small)

@@ -12,57 +12,26 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
+from gpu_checks import dev  # noqa: E402,F401
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 SIZES = [1, 31, 32, 33, 1024, 4095, 4096, 4097]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def _frames(oracle_mod, n, seed):
-    win, lens = oracle_mod.synth(abi.SYN_FUZZ, n, seed, stride=80)
-    out = []
-    for i in range(n):
-        L = min(int(lens[i]), 2048)
-        f = win[i * 80:(i + 1) * 80].tobytes()
-        out.append((f + bytes(max(0, L - 80)))[:L])
-    return out
-
-
-def _expect(oracle_mod, frames, cfg):
-    c = oracle_mod.cfg(*cfg)
-    want = [oracle_mod.toeplitz_dispatch(f, len(f), c) for f in frames]
-    q = np.array([x for x, _ in want], np.int16)
-    h = np.array([y for _, y in want], np.uint32)
-    qi, qs = oracle_mod.process_burst(q, cfg[1])
-    return q, h, qi, qs
-
-
-def _check(r, q, h, qi, qs):
-    assert np.array_equal(np.asarray(r.q), q)
-    assert np.array_equal(np.asarray(r.hash), h)
-    assert np.array_equal(np.asarray(r.qidx), qi)
-    assert np.array_equal(np.asarray(r.qstart)[: qs.size], qs)
 
 
 @pytest.mark.parametrize("n", SIZES)
 def test_small_burst_all_host_apis(dev, oracle_mod, n):
     cfg = (5, 4, 1, 1)
-    frames = _frames(oracle_mod, n, 1000 + n)
-    q, h, qi, qs = _expect(oracle_mod, frames, cfg)
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=131)
+    frames = synth_frames(oracle_mod, n, 1000 + n)
+    q, h, qi, qs = expect_lists(oracle_mod, frames, cfg)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=131)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
-        _check(eng.dispatch_frames(frames), q, h, qi, qs)
-        _check(eng.dispatch_burst(ptrs, write_rss=True), q, h, qi, qs)
+        check_lists(eng.dispatch_frames(frames), q, h, qi, qs)
+        check_lists(eng.dispatch_burst(ptrs, write_rss=True), q, h, qi, qs)
         rss = pool.reshape(-1, stride)[:, 44:48].copy().view(np.uint32).ravel()
         assert np.array_equal(rss, h)
         pool.reshape(-1, stride)[:, 44:48] = 0
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
-        _check(eng.dispatch_burst_zc(ptrs, write_rss=True), q, h, qi, qs)
+        check_lists(eng.dispatch_burst_zc(ptrs, write_rss=True), q, h, qi, qs)
         rss = pool.reshape(-1, stride)[:, 44:48].copy().view(np.uint32).ravel()
         assert np.array_equal(rss, h)
         # frames_zc with pageable pointer/length arrays (staged by the library)
@@ -85,9 +54,9 @@ def test_small_burst_all_host_apis(dev, oracle_mod, n):
 def test_small_burst_registered_outputs(dev, oracle_mod):
     """Outputs in registered memory are written by the kernel in place."""
     n, cfg = 1500, (8, 8, 1, 0)
-    frames = _frames(oracle_mod, n, 77)
-    q, h, qi, qs = _expect(oracle_mod, frames, cfg)
-    pool, ptrs, _ = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle_mod, n, 77)
+    q, h, qi, qs = expect_lists(oracle_mod, frames, cfg)
+    pool, ptrs, _ = fake_mbufs(frames, headroom=128)
     raw = np.zeros(n * 32 + 3 * 4096, np.uint8)
     off = (-raw.ctypes.data) % 4096
     arena = raw[off: off + n * 32 + 4096]
@@ -114,15 +83,15 @@ def test_small_burst_registered_outputs(dev, oracle_mod):
 def test_small_burst_bucket_limit(dev, oracle_mod, nq):
     """nb = nb_queues + 1 <= 64 takes the one-launch path; 65 falls back."""
     cfg = (64, nq, 1, 0)
-    frames = _frames(oracle_mod, 3000, nq)
-    q, h, qi, qs = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, 3000, nq)
+    q, h, qi, qs = expect_lists(oracle_mod, frames, cfg)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
-        _check(eng.dispatch_frames(frames), q, h, qi, qs)
+        check_lists(eng.dispatch_frames(frames), q, h, qi, qs)
 
 
 def test_small_burst_fault_reported(dev, oracle_mod):
-    frames = _frames(oracle_mod, 100, 5)
-    pool, ptrs, _ = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, 100, 5)
+    pool, ptrs, _ = fake_mbufs(frames)
     with SoftRss(3, 3, 1, 1, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
         bad = ptrs.copy()
@@ -130,14 +99,14 @@ def test_small_burst_fault_reported(dev, oracle_mod):
         with pytest.raises(abi.YrssError):
             eng.dispatch_burst_zc(bad)
         r = eng.dispatch_burst_zc(ptrs)          # the fault does not stick
-        q, h, qi, qs = _expect(oracle_mod, frames, (3, 3, 1, 1))
-        _check(r, q, h, qi, qs)
+        q, h, qi, qs = expect_lists(oracle_mod, frames, (3, 3, 1, 1))
+        check_lists(r, q, h, qi, qs)
         eng.unregister_host_memory(pool.ctypes.data)
 
 
 @pytest.mark.parametrize("n", [32, 2000, 9000])
 def test_small_and_multi_kernel_paths_agree(dev, oracle_mod, n, monkeypatch):
-    frames = _frames(oracle_mod, n, 4242)
+    frames = synth_frames(oracle_mod, n, 4242)
     outs = []
     for one_launch in (0, 2):   # default / never (multi-kernel path)
         with SoftRss(3, 3, 1, 1, device=0, max_burst=0) as eng:
@@ -147,8 +116,8 @@ def test_small_and_multi_kernel_paths_agree(dev, oracle_mod, n, monkeypatch):
     a, b = outs
     for f in ("q", "hash", "qidx", "qstart"):
         assert np.array_equal(np.asarray(getattr(a, f)), np.asarray(getattr(b, f))), f
-    q, h, qi, qs = _expect(oracle_mod, frames, (3, 3, 1, 1))
-    _check(a, q, h, qi, qs)
+    q, h, qi, qs = expect_lists(oracle_mod, frames, (3, 3, 1, 1))
+    check_lists(a, q, h, qi, qs)
 
 
 @pytest.mark.parametrize("n", [1000, 6000])   # one-launch path / multi-kernel path
@@ -156,10 +125,10 @@ def test_async_bursts_over_two_contexts(dev, oracle_mod, n):
     """YRSS_F_ASYNC: bursts in flight on two contexts sharing one registered
     pool; -EBUSY for a second burst on a busy context; yrss_wait delivers."""
     cfg = (5, 4, 1, 1)
-    frames = _frames(oracle_mod, 2 * n, 99)
-    q, h, qi, qs = _expect(oracle_mod, frames[:n], cfg)
-    q2, h2, qi2, qs2 = _expect(oracle_mod, frames[n:], cfg)
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle_mod, 2 * n, 99)
+    q, h, qi, qs = expect_lists(oracle_mod, frames[:n], cfg)
+    q2, h2, qi2, qs2 = expect_lists(oracle_mod, frames[n:], cfg)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=128)
     lib = abi.load()
     outs = [(np.empty(n, np.int16), np.empty(n, np.uint32), np.empty(n, np.uint32),
              np.empty(cfg[1] + 2, np.uint32)) for _ in range(2)]
@@ -186,16 +155,16 @@ def test_async_bursts_over_two_contexts(dev, oracle_mod, n):
         assert np.array_equal(rss, np.concatenate([h, h2]))
         # dropping one context's registration keeps the other's working
         e0.unregister_host_memory(pool.ctypes.data)
-        _check(e1.dispatch_burst_zc(ptrs[:n]), q, h, qi, qs)
+        check_lists(e1.dispatch_burst_zc(ptrs[:n]), q, h, qi, qs)
         e1.unregister_host_memory(pool.ctypes.data)
 
 
 def test_async_staged_and_frames(dev, oracle_mod):
     cfg = (8, 8, 1, 0)
     n = 3000
-    frames = _frames(oracle_mod, n, 7)
-    q, h, qi, qs = _expect(oracle_mod, frames, cfg)
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=130)
+    frames = synth_frames(oracle_mod, n, 7)
+    q, h, qi, qs = expect_lists(oracle_mod, frames, cfg)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=130)
     data = (ptrs + np.uint64(128 + 130)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
     lib = abi.load()
@@ -225,17 +194,17 @@ def test_async_python_wrapper(dev, oracle_mod):
     """SoftRss.dispatch_burst(_zc)(async_=True) + wait() on two engines."""
     cfg = (3, 3, 1, 1)
     n = 2500
-    frames = _frames(oracle_mod, 2 * n, 321)
-    want = [_expect(oracle_mod, frames[:n], cfg), _expect(oracle_mod, frames[n:], cfg)]
-    pool, ptrs, _ = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, 2 * n, 321)
+    want = [expect_lists(oracle_mod, frames[:n], cfg), expect_lists(oracle_mod, frames[n:], cfg)]
+    pool, ptrs, _ = fake_mbufs(frames)
     with SoftRss(*cfg, device=0, max_burst=0) as e0, SoftRss(*cfg, device=0, max_burst=0) as e1:
         r0 = e0.dispatch_burst(ptrs[:n], async_=True)
         e1.register_host_memory(pool.ctypes.data, pool.nbytes)
         r1 = e1.dispatch_burst_zc(ptrs[n:], async_=True)
         e0.wait()
         e1.wait()
-        _check(r0, *want[0])
-        _check(r1, *want[1])
+        check_lists(r0, *want[0])
+        check_lists(r1, *want[1])
         e1.unregister_host_memory(pool.ctypes.data)
 
 

@@ -13,14 +13,8 @@ pytestmark = pytest.mark.gpu
 
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _check, _expect, _frames  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
+from gpu_checks import dev  # noqa: E402,F401
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 
 @pytest.mark.parametrize("nslots,nblocks", [(16, 4), (8, 1), (32, 8)])
@@ -29,9 +23,9 @@ def test_worker_bursts_vs_oracle(dev, oracle_mod, nslots, nblocks):
     rng = np.random.default_rng(nslots * 100 + nblocks)
     sizes = [1, 32, 1024, 0, 33, 64, 1000, 7] + list(rng.integers(1, 1025, 30))
     total = int(sum(sizes))
-    frames = _frames(oracle_mod, total, 4000 + nslots)
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=129)
-    q_all, h_all, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, total, 4000 + nslots)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=129)
+    q_all, h_all, _, _ = expect_lists(oracle_mod, frames, cfg)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
         eng.worker_start(nslots, nblocks)
@@ -61,16 +55,16 @@ def _verify(eng, oracle_mod, tickets, offs, sizes, q_all, h_all, cfg):
     r = eng.worker_poll(t)
     q = q_all[off:off + n]
     qi, qs = oracle_mod.process_burst(q, cfg[1])
-    _check(r, q, h_all[off:off + n], qi, qs)
+    check_lists(r, q, h_all[off:off + n], qi, qs)
 
 
 def test_worker_idle_exit_and_relaunch(dev, oracle_mod, monkeypatch):
     monkeypatch.setenv("YRSS_WORKER_IDLE_MS", "5")
     monkeypatch.setenv("YRSS_WORKER_LIFE_MS", "200")
     cfg = (3, 3, 1, 1)
-    frames = _frames(oracle_mod, 600, 9)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q, h, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, 600, 9)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q, h, _, _ = expect_lists(oracle_mod, frames, cfg)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
         eng.worker_start(4, 2)
@@ -79,14 +73,14 @@ def test_worker_idle_exit_and_relaunch(dev, oracle_mod, monkeypatch):
             t = eng.worker_submit(ptrs[lo:lo + 100])
             r = eng.worker_poll(t)
             qi, qs = oracle_mod.process_burst(q[lo:lo + 100], 3)
-            _check(r, q[lo:lo + 100], h[lo:lo + 100], qi, qs)
+            check_lists(r, q[lo:lo + 100], h[lo:lo + 100], qi, qs)
             time.sleep(0.03 if k % 2 == 0 else 0.25)   # past the idle / lifetime limits
         # registering more memory restarts the worker with the new range table
-        extra = _frames(oracle_mod, 50, 10)
-        pool2, ptrs2, _ = _fake_mbufs(extra)
+        extra = synth_frames(oracle_mod, 50, 10)
+        pool2, ptrs2, _ = fake_mbufs(extra)
         eng.register_host_memory(pool2.ctypes.data, pool2.nbytes)
-        q2, h2, qi2, qs2 = _expect(oracle_mod, extra, cfg)
-        _check(eng.worker_poll(eng.worker_submit(ptrs2)), q2, h2, qi2, qs2)
+        q2, h2, qi2, qs2 = expect_lists(oracle_mod, extra, cfg)
+        check_lists(eng.worker_poll(eng.worker_submit(ptrs2)), q2, h2, qi2, qs2)
         eng.worker_stop()
         eng.unregister_host_memory(pool2.ctypes.data)
         eng.unregister_host_memory(pool.ctypes.data)
@@ -94,8 +88,8 @@ def test_worker_idle_exit_and_relaunch(dev, oracle_mod, monkeypatch):
 
 def test_worker_errors(dev, oracle_mod):
     cfg = (3, 3, 1, 1)
-    frames = _frames(oracle_mod, 1100, 12)
-    pool, ptrs, _ = _fake_mbufs(frames)
+    frames = synth_frames(oracle_mod, 1100, 12)
+    pool, ptrs, _ = fake_mbufs(frames)
     lib = abi.load()
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         assert lib.yrss_worker_start(eng._ctx, 6, 4) == -22          # nslots % nblocks
@@ -112,8 +106,8 @@ def test_worker_errors(dev, oracle_mod):
             eng.worker_submit(ptrs[:5])                               # both slots unpolled
         with pytest.raises(abi.YrssError):
             eng.worker_poll(tb)                                       # -EFAULT
-        q, h, qi, qs = _expect(oracle_mod, frames[:20], cfg)
-        _check(eng.worker_poll(t2), q, h, qi, qs)
+        q, h, qi, qs = expect_lists(oracle_mod, frames[:20], cfg)
+        check_lists(eng.worker_poll(t2), q, h, qi, qs)
         eng.worker_stop()
         eng.unregister_host_memory(pool.ctypes.data)
 
@@ -123,11 +117,11 @@ def test_worker_frames(dev, oracle_mod):
     the windows."""
     cfg = (8, 8, 1, 0)
     sizes = [32, 1, 1024, 500, 0, 77]
-    frames = _frames(oracle_mod, sum(sizes), 55)
-    pool, ptrs, _ = _fake_mbufs(frames, headroom=130)
+    frames = synth_frames(oracle_mod, sum(sizes), 55)
+    pool, ptrs, _ = fake_mbufs(frames, headroom=130)
     data = (ptrs + np.uint64(128 + 130)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
-    q_all, h_all, _, _ = _expect(oracle_mod, frames, cfg)
+    q_all, h_all, _, _ = expect_lists(oracle_mod, frames, cfg)
     lib = abi.load()
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
@@ -161,8 +155,8 @@ def test_worker_windows(dev, oracle_mod, stride):
     GPU reads only the staging, bit-identical to the frames form."""
     cfg = (8, 8, 1, 0)
     sizes = [32, 1, 1024, 500, 0, 77, 1000]
-    frames = _frames(oracle_mod, sum(sizes), 56 + stride)
-    q_all, h_all, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, sum(sizes), 56 + stride)
+    q_all, h_all, _, _ = expect_lists(oracle_mod, frames, cfg)
     lens = np.array([len(f) for f in frames], np.uint16)
     raw = np.zeros(len(frames) * stride + 128, np.uint8)
     win = raw[(-raw.ctypes.data) % 64:]                      # 64-byte aligned staging
@@ -179,7 +173,7 @@ def test_worker_windows(dev, oracle_mod, stride):
             r = eng.worker_poll(t)
             qr = q_all[off:off + n]
             qi_ref, qs_ref = oracle_mod.process_burst(qr, cfg[1])
-            _check(r, qr, h_all[off:off + n], qi_ref, qs_ref)
+            check_lists(r, qr, h_all[off:off + n], qi_ref, qs_ref)
             off += n
         with pytest.raises(abi.YrssError):
             eng.worker_submit_windows(win, 0, lens[:4])       # stride below a window
@@ -194,9 +188,9 @@ def test_worker_low_rate_no_stall(dev, oracle_mod, monkeypatch):
     monkeypatch.setenv("YRSS_WORKER_IDLE_MS", "20")
     cfg = (4, 4, 1, 1)
     nb, per, nburst = 8, 16, 40
-    frames = _frames(oracle_mod, per * nburst, 77)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q, h, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, per * nburst, 77)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q, h, _, _ = expect_lists(oracle_mod, frames, cfg)
     lat = []
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
@@ -208,7 +202,7 @@ def test_worker_low_rate_no_stall(dev, oracle_mod, monkeypatch):
             r = eng.worker_poll(t)
             lat.append(time.perf_counter() - t0)
             qi, qs = oracle_mod.process_burst(q[lo:lo + per], cfg[1])
-            _check(r, q[lo:lo + per], h[lo:lo + per], qi, qs)
+            check_lists(r, q[lo:lo + per], h[lo:lo + per], qi, qs)
             time.sleep(0.005)        # each workgroup sees a burst every ~40 ms
         eng.worker_stop()
         eng.unregister_host_memory(pool.ctypes.data)
@@ -222,9 +216,9 @@ def test_worker_relaunch_nonblocking_poll(dev, oracle_mod, monkeypatch):
     the burst served: the poll relaunches."""
     monkeypatch.setenv("YRSS_WORKER_IDLE_MS", "2")
     cfg = (3, 3, 1, 1)
-    frames = _frames(oracle_mod, 64, 78)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q, h, qi, qs = _expect(oracle_mod, frames[:32], cfg)
+    frames = synth_frames(oracle_mod, 64, 78)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q, h, qi, qs = expect_lists(oracle_mod, frames[:32], cfg)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
         eng.worker_start(4, 4)
@@ -234,7 +228,7 @@ def test_worker_relaunch_nonblocking_poll(dev, oracle_mod, monkeypatch):
             while r is None and time.time() < deadline:
                 r = eng.worker_poll(t, wait=False)
             assert r is not None
-            _check(r, q, h, qi, qs)
+            check_lists(r, q, h, qi, qs)
             time.sleep(0.02)         # past the idle limit: every workgroup leaves
         eng.worker_stop()
         eng.unregister_host_memory(pool.ctypes.data)
@@ -247,9 +241,9 @@ def test_worker_then_device_batch(dev, oracle_mod, monkeypatch):
     monkeypatch.setenv("YRSS_WORKER_IDLE_MS", "3000")
     monkeypatch.setenv("YRSS_WORKER_LIFE_MS", "3000")
     cfg = (3, 3, 1, 1)
-    frames = _frames(oracle_mod, 256, 91)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q, h, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, 256, 91)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q, h, _, _ = expect_lists(oracle_mod, frames, cfg)
     n = 1 << 20
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
@@ -271,7 +265,7 @@ def test_worker_then_device_batch(dev, oracle_mod, monkeypatch):
         assert np.array_equal(res.hash[:4096].cpu().numpy().view(np.uint32), h_ref)
         r = eng.worker_poll(t_b)                          # relaunched by the poll
         qi, qs = oracle_mod.process_burst(q[128:256], cfg[1])
-        _check(r, q[128:256], h[128:256], qi, qs)
+        check_lists(r, q[128:256], h[128:256], qi, qs)
         eng.worker_stop()
         eng.unregister_host_memory(pool.ctypes.data)
 
@@ -283,9 +277,9 @@ def test_worker_direct_outputs(dev, oracle_mod):
     range a pending burst may touch cannot be unregistered (-EBUSY)."""
     cfg = (5, 4, 1, 1)
     sizes = [32, 1024, 7, 500, 32, 1]
-    frames = _frames(oracle_mod, sum(sizes), 66)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q_all, h_all, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, sum(sizes), 66)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q_all, h_all, _, _ = expect_lists(oracle_mod, frames, cfg)
     lib = abi.load()
     arena = np.zeros(1 << 20, np.uint8)
     with SoftRss(*cfg, device=0, max_burst=0) as eng:
@@ -340,9 +334,9 @@ def test_worker_per_slot_outputs(dev, oracle_mod, registered):
     nslots, nblocks = 8, 2
     rng = np.random.default_rng(5)
     sizes = [int(x) for x in rng.integers(1, 300, 48)]
-    frames = _frames(oracle_mod, sum(sizes), 88)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q_all, h_all, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, sum(sizes), 88)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q_all, h_all, _, _ = expect_lists(oracle_mod, frames, cfg)
     lib = abi.load()
     arena = np.zeros(nslots * 4096, np.uint8)
     outs = []
@@ -413,9 +407,9 @@ def test_device_batch_beside_other_contexts_worker(dev, oracle_mod, monkeypatch)
     monkeypatch.setenv("YRSS_WORKER_IDLE_MS", "8000")
     monkeypatch.setenv("YRSS_WORKER_LIFE_MS", "10000")
     cfg = (3, 3, 1, 1)
-    frames = _frames(oracle_mod, 256, 21)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q, h, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, 256, 21)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q, h, _, _ = expect_lists(oracle_mod, frames, cfg)
     n = 1 << 24
     with SoftRss(*cfg, device=0, max_burst=0) as b_eng, \
             SoftRss(*cfg, device=0, max_burst=0) as a_eng:
@@ -426,11 +420,11 @@ def test_device_batch_beside_other_contexts_worker(dev, oracle_mod, monkeypatch)
         a_eng.register_host_memory(pool.ctypes.data, pool.nbytes)
         a_eng.worker_start(512, 128)
         r = a_eng.worker_poll(a_eng.worker_submit(ptrs[:128]))   # resident now
-        _check(r, q[:128], h[:128], *oracle_mod.process_burst(q[:128], 3))
+        check_lists(r, q[:128], h[:128], *oracle_mod.process_burst(q[:128], 3))
         shared = _batch_ms(b_eng, win, lens, n, reps=1, filt=True)
         assert shared < solo + 5.0, (solo, shared)
         r = a_eng.worker_poll(a_eng.worker_submit(ptrs[128:256]))
-        _check(r, q[128:], h[128:], *oracle_mod.process_burst(q[128:], 3))
+        check_lists(r, q[128:], h[128:], *oracle_mod.process_burst(q[128:], 3))
         a_eng.worker_stop()
         a_eng.unregister_host_memory(pool.ctypes.data)
 
@@ -443,20 +437,19 @@ os.environ["YRSS_WORKER_LIFE_MS"] = "10000"
 import numpy as np
 from oracle import oracle
 from yastack_amd import SoftRss
-from test_gpu_parity import _fake_mbufs
-from test_gpu_small_burst import _check, _expect, _frames
-frames = _frames(oracle, 128, 33)
-pool, ptrs, _ = _fake_mbufs(frames)
-q, h, _, _ = _expect(oracle, frames, (3, 3, 1, 1))
+from hostbufs import check_lists, expect_lists, fake_mbufs, synth_frames
+frames = synth_frames(oracle, 128, 33)
+pool, ptrs, _ = fake_mbufs(frames)
+q, h, _, _ = expect_lists(oracle, frames, (3, 3, 1, 1))
 with SoftRss(3, 3, 1, 1, device=0, max_burst=0) as eng:
     eng.register_host_memory(pool.ctypes.data, pool.nbytes)
     eng.worker_start(512, 128)
-    _check(eng.worker_poll(eng.worker_submit(ptrs[:64])), q[:64], h[:64],
-           *oracle.process_burst(q[:64], 3))
+    check_lists(eng.worker_poll(eng.worker_submit(ptrs[:64])), q[:64], h[:64],
+                *oracle.process_burst(q[:64], 3))
     print("ready", flush=True)
     sys.stdin.readline()
-    _check(eng.worker_poll(eng.worker_submit(ptrs[64:])), q[64:], h[64:],
-           *oracle.process_burst(q[64:], 3))
+    check_lists(eng.worker_poll(eng.worker_submit(ptrs[64:])), q[64:], h[64:],
+                *oracle.process_burst(q[64:], 3))
     eng.worker_stop()
     eng.unregister_host_memory(pool.ctypes.data)
 print("ok", flush=True)
@@ -501,9 +494,9 @@ def test_worker_guard_fault_is_per_burst(dev, oracle_mod):
 
     cfg = (8, 8, 1, 0)
     nb, per = 12, 40
-    frames = _frames(oracle_mod, nb * per, 77)
-    pool, ptrs, _ = _fake_mbufs(frames)
-    q_all, h_all, _, _ = _expect(oracle_mod, frames, cfg)
+    frames = synth_frames(oracle_mod, nb * per, 77)
+    pool, ptrs, _ = fake_mbufs(frames)
+    q_all, h_all, _, _ = expect_lists(oracle_mod, frames, cfg)
     with SoftRss(*cfg, device=0, max_burst=0, lib_path=str(abi.TEST_LIB_PATH)) as eng:
         assert eng._lib.yrss_debug_worker_inject(eng._ctx, 5) == 0   # ticket 5 fires a guard
         eng.register_host_memory(pool.ctypes.data, pool.nbytes)
@@ -518,13 +511,13 @@ def test_worker_guard_fault_is_per_burst(dev, oracle_mod):
                 continue
             r = eng.worker_poll(t)
             qi, qs = oracle_mod.process_burst(q, cfg[1])
-            _check(r, q, h_all[i * per:(i + 1) * per], qi, qs)
+            check_lists(r, q, h_all[i * per:(i + 1) * per], qi, qs)
         code, kernel, where, value = eng.fault_info()
         assert (code, kernel, where, value) == (abi.FAULT_LIST_RANGE, abi.K_WORKER, 5, 0xdead)
         assert eng.fault_info()[0] == abi.FAULT_NONE
         # later bursts are unaffected
         t = eng.worker_submit(ptrs[:per])
         qi, qs = oracle_mod.process_burst(q_all[:per], cfg[1])
-        _check(eng.worker_poll(t), q_all[:per], h_all[:per], qi, qs)
+        check_lists(eng.worker_poll(t), q_all[:per], h_all[:per], qi, qs)
         eng.worker_stop()
         eng.unregister_host_memory(pool.ctypes.data)

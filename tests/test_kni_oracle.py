@@ -5,11 +5,9 @@ The reference has no tests for these; every expectation below is derived by
 hand from fs/lib/ff_dpdk_kni.c:51-118,218-290 and ff_dpdk_if.c:976-996,
 1058-1140 and says which line it exercises.
 """
-import struct
-
 import numpy as np
 
-from frames import ethertype_frame, ipv4_frame
+from frames import ethertype_frame, ipip_frame, ipv4_frame
 
 
 def ports_of(bm):
@@ -61,18 +59,6 @@ def test_protocol_filter_cases(oracle_mod):
     assert pf(ipv4_frame(*base, 53, proto=17), 14 + 20 + 8) == 2   # UDP hdr = 8 is enough
     assert pf(ipv4_frame(*base, 53, proto=17), 14 + 20 + 7) == -1
     assert pf(ethertype_frame(0x86DD), 64) == -1
-
-
-def ipip_frame(inner_ihl, inner_proto, dport, outer_ihl=5, length=80):
-    b = bytearray(ipv4_frame("10.0.0.1", 1, "10.0.0.2", 2, proto=4, ihl=outer_ihl,
-                             length=length, ports_at_l4=False))
-    o = 14 + 4 * outer_ihl
-    b[o] = 0x40 | inner_ihl
-    b[o + 9] = inner_proto
-    p = o + 4 * inner_ihl
-    if inner_ihl >= 3 and p + 4 <= len(b):      # ports must not overwrite the header
-        struct.pack_into(">HH", b, p, 1111, dport)
-    return bytes(b)
 
 
 def test_protocol_filter_ipip(oracle_mod):

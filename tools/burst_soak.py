@@ -22,8 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import oracle  # noqa: E402  (checker only)
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _expect, _frames  # noqa: E402
+from hostbufs import expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 
 def main():
@@ -34,11 +33,11 @@ def main():
     rng = np.random.default_rng(args.seed)
     cfg = (5, 4, 1, 1)
     npool = 1 << 15
-    frames = _frames(oracle, npool, 4321)
-    pool, ptrs, stride = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle, npool, 4321)
+    pool, ptrs, stride = fake_mbufs(frames, headroom=128)
     data = (ptrs + np.uint64(256)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
-    q_all, h_all, _, _ = _expect(oracle, frames, cfg)
+    q_all, h_all, _, _ = expect_lists(oracle, frames, cfg)
     lib = abi.load()
     stats = dict(bursts=0, pkts=0, small=0, big=0, asyncs=0, writeback=0)
     engs = [SoftRss(*cfg, device=0, max_burst=0) for _ in range(2)]

@@ -22,8 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import oracle  # noqa: E402  (checker only)
 from yastack_amd import FanOut, SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _expect, _frames  # noqa: E402
+from hostbufs import expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 
 def main():
@@ -38,11 +37,11 @@ def main():
     rng = np.random.default_rng(args.seed)
     cfg = (6, 5, 1, 1)
     npool = 1 << 15
-    frames = _frames(oracle, npool, 4321)
-    pool, ptrs, _ = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle, npool, 4321)
+    pool, ptrs, _ = fake_mbufs(frames, headroom=128)
     data = (ptrs + np.uint64(256)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
-    q_all, h_all, _, _ = _expect(oracle, frames, cfg)
+    q_all, h_all, _, _ = expect_lists(oracle, frames, cfg)
     stats = dict(bursts=0, pkts=0, nonblock=0, gaps=0, dev_batches=0, runs=0)
     t_end = time.time() + args.seconds
     with SoftRss(*cfg, device=0, max_burst=0) as dev_eng:

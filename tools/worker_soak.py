@@ -22,8 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import oracle  # noqa: E402  (checker only)
 from yastack_amd import SoftRss, abi  # noqa: E402
 
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _expect, _frames  # noqa: E402
+from hostbufs import expect_lists, fake_mbufs, synth_frames  # noqa: E402
 
 
 def main():
@@ -38,11 +37,11 @@ def main():
     rng = np.random.default_rng(args.seed)
     cfg = (6, 5, 1, 1)
     npool = 1 << 15
-    frames = _frames(oracle, npool, 1234)
-    pool, ptrs, _ = _fake_mbufs(frames, headroom=128)
+    frames = synth_frames(oracle, npool, 1234)
+    pool, ptrs, _ = fake_mbufs(frames, headroom=128)
     data = (ptrs + np.uint64(256)).astype(np.uint64)
     flen = np.array([len(f) for f in frames], np.uint16)
-    q_all, h_all, _, _ = _expect(oracle, frames, cfg)
+    q_all, h_all, _, _ = expect_lists(oracle, frames, cfg)
     lib = abi.load()
     nslots, nblocks = 32, 8
     arena = np.zeros(nslots * 16384, np.uint8)

@@ -14,14 +14,13 @@ os.environ.setdefault("YRSS_WORKER_IDLE_MS", "3000")
 os.environ.setdefault("YRSS_WORKER_LIFE_MS", "6000")
 import torch  # noqa: E402
 
+from hostbufs import fake_mbufs, synth_frames  # noqa: E402
 from oracle import oracle  # noqa: E402
-from test_gpu_parity import _fake_mbufs  # noqa: E402
-from test_gpu_small_burst import _frames  # noqa: E402
 from yastack_amd import SoftRss, abi  # noqa: E402
 
 n = 1 << 24
-frames = _frames(oracle, 256, 3)
-pool, ptrs, _ = _fake_mbufs(frames)
+frames = synth_frames(oracle, 256, 3)
+pool, ptrs, _ = fake_mbufs(frames)
 filt = "--filter" in sys.argv
 with SoftRss(3, 3, 1, 1, device=0, max_burst=0) as b, SoftRss(3, 3, 1, 1, device=0, max_burst=0) as a:
     win, lens = b.synth(abi.SYN_UDP4, n)

@@ -52,8 +52,9 @@ extern "C" {
 /* Queue written for a hashed TCP packet whose L4 ports lie beyond the bytes
  * the caller staged in its header window (only possible when win_stride < 78
  * and data_len > win_stride).  Never produced by yrss_dispatch_burst /
- * yrss_dispatch_frames, which always stage enough bytes.  Such packets land
- * in the drop bucket, like any ret outside [0, nb_queues). */
+ * yrss_dispatch_frames, which always stage enough bytes (on the reference's
+ * rules; see yrss_set_extended for tagged IPv4 with a large IHL).  Such packets
+ * land in the drop bucket, like any ret outside [0, nb_queues). */
 #define YRSS_Q_TRUNCATED (-2)
 
 /* Widest header window the parse ever needs: with IHL=15 the TCP ports sit at
@@ -183,6 +184,62 @@ int yrss_dispatch_dev(yrss_ctx *ctx, const uint8_t *d_win, uint32_t win_stride,
  * otherwise the worker is halted and relaunched by the next submit. */
 int yrss_set_kni(yrss_ctx *ctx, int enable, const char *method,
                  const char *tcp_ports, const char *udp_ports);
+
+/* ---- extended mode: THIS BUILD'S OWN SEMANTICS, NOT fs/lib's ------------------ */
+
+/* toeplitz_dispatch hashes untagged IPv4/TCP and nothing else: every UDP, IPv6
+ * or VLAN-tagged packet gets the constant queue 2 (ff_dpdk_if.c:2050-2112).
+ * That is the default here too, bit for bit.  The flags below are an opt-in
+ * departure from the reference, per context, for deployments that want the
+ * flows they carry spread; nothing in fs/lib computes these results, and the
+ * hashes are validated against the 82599 datasheet vectors instead
+ * (tests/golden/thash_82599.json).  The rules, applied in this order:
+ *   YRSS_EXT_VLAN  The frame is classified as if hardware vlan_strip had
+ *                  removed its tags: ethertype 0x8100 or 0x88A8 at byte 12
+ *                  moves the L3 offset o to 18 (ethertype at byte 16); 0x8100
+ *                  there again moves it to 22 (ethertype at byte 20); at most
+ *                  two tags.  Every later rule sees the frame without its t
+ *                  tags and with len - 4t, the reference's length quirks
+ *                  included.  A frame too short to hold the tag(s) and the
+ *                  inner ethertype is unhashed (queue 2); ARP / RARP under a
+ *                  tag is queue 0.
+ *   IPv4           The reference's rule (:1968-2035) on the stripped frame.
+ *                  With YRSS_EXT_UDP protocol 17 takes the TCP branch: the
+ *                  same checks, the same tuple bytes in the same order
+ *                  (:1998-2021), the same hash % d (+1).
+ *   YRSS_EXT_IPV6  Ethertype 0x86DD with len - o >= 44 and next-header
+ *                  (byte o + 6) 6, or 17 with YRSS_EXT_UDP: the hash is the
+ *                  Toeplitz of the 36 bytes src | dst | sport | dport in wire
+ *                  order (the 82599 "l3l4" input), the queue as for hashed
+ *                  TCP.  No extension-header walk: any other next-header is
+ *                  unhashed.  Key bytes past rss_key_len count as zero, as in
+ *                  toeplitz_hash (:1896).
+ * Everything else is as without flags: queue 2 and hash 0, queue 0 for ARP /
+ * RARP.  The window rule is unchanged: ports that end beyond the staged window
+ * (o + 4 IHL + 4, or o + 44 for IPv6, > win_stride) give YRSS_Q_TRUNCATED.  At
+ * stride 64 that now takes two tags with IPv6 or tags with a large IHL; at
+ * YRSS_WIN_FULL (what the host bursts stage) only tagged IPv4 with
+ * 4 t + 4 IHL > 62 (IHL 15 under one tag, 14 or 15 under two), which the host
+ * bursts can therefore produce under YRSS_EXT_VLAN; QinQ + IPv6 ends at byte 66.
+ * The protocol_filter class (filter outputs, route classes, yrss_route_burst)
+ * keeps following the reference on the unstripped frame.
+ *
+ * Honoured by every yrss_dispatch_dev*, yrss_route_dev_seg, the host bursts
+ * and frames (zero-copy and routed forms included) and by
+ * yrss_toeplitz_dispatch on a context without a worker.  NOT by the
+ * persistent worker: while flags are set yrss_worker_start*, every
+ * yrss_worker_submit* and so the shim on a worker context are refused
+ * (-ENOTSUP; the shim returns -1).  The helper process and the fan-out own
+ * their contexts and stay on the reference's rules.
+ *
+ * flags == 0 restores the reference's rules exactly.  -EINVAL on unknown
+ * bits; -EBUSY while a YRSS_F_ASYNC or worker burst is pending; a resident
+ * worker is halted (the next submit after flags return to 0 relaunches it). */
+#define YRSS_EXT_VLAN 0x1u
+#define YRSS_EXT_IPV6 0x2u
+#define YRSS_EXT_UDP  0x4u
+#define YRSS_EXT_ALL  0x7u
+int yrss_set_extended(yrss_ctx *ctx, uint32_t flags);
 
 /* Full device batch: yrss_dispatch_dev plus the optional filter output. */
 struct yrss_dev_batch {

@@ -15,7 +15,7 @@ own max - min over its repeats.  The base is the first leg given.
 A leg is [name=]lib[@k=v;k=v][:form].  lib: cur, test (libyrss_test.so) or a
 path, relative to the repository root or absolute (tools/build_ab_lib.sh).
 k=v: yrss_set_tuning fields, side=1 (the batches on a non-default stream),
-dbg_groups / dbg_merge (the test library's hooks); dev legs only.  form, dev:
+ext=N (yrss_set_extended flags: 1 VLAN, 2 IPv6, 4 UDP), dbg_groups / dbg_merge (the test library's hooks); dev legs only.  form, dev:
 global (default), seg, seg-filter, route; worker: plain (default), route.
 
 dev times --steps back-to-back batches by wall clock (step, ms, no events) and,
@@ -52,7 +52,7 @@ from yastack_amd import SoftRss, abi  # noqa: E402
 Leg = namedtuple("Leg", "name lib tune form")
 
 PROFILES = {"udp4": abi.SYN_UDP4, "tcp4": abi.SYN_TCP4, "imix": abi.SYN_IMIX,
-            "jumbo_tcp4": abi.SYN_JUMBO_TCP4}
+            "jumbo_tcp4": abi.SYN_JUMBO_TCP4, "vlan6_tcp": abi.SYN_VLAN6_TCP}
 KERNELS = {"parse": abi.K_PARSE_HASH, "scan": abi.K_SCAN, "scatter": abi.K_SCATTER}
 # dev form: (call, allocator, want_filter, kernels timed, needs KNI)
 DEV_FORMS = {
@@ -163,6 +163,9 @@ def run_dev_leg(leg, rng, args, npr, profile):
     # side=1: the caller's work on a non-default (non-blocking) stream
     st = torch.cuda.Stream() if tn.pop("side", 0) else None
     grp = tn.pop("dbg_groups", 0)
+    ext = tn.pop("ext", 0)
+    if ext:
+        e.set_extended(vlan=bool(ext & 1), ipv6=bool(ext & 2), udp=bool(ext & 4))
     if tn.pop("dbg_merge", 0):
         assert e._lib.yrss_debug_partial_merge(e._ctx, 1) == 0
     if grp:

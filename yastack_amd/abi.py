@@ -40,6 +40,9 @@ ROUTE_SEG_MAX_QUEUES = 13
 ROUTE_LISTS_MAX_QUEUES = 61
 F_WRITE_RSS = 0x1
 F_ASYNC = 0x2
+# extended mode (yrss_set_extended): this build's own semantics, not fs/lib's
+EXT_VLAN, EXT_IPV6, EXT_UDP = 0x1, 0x2, 0x4
+EXT_ALL = EXT_VLAN | EXT_IPV6 | EXT_UDP
 
 K_PARSE_HASH, K_SCAN, K_SCATTER = 0, 1, 2
 K_BURST, K_WORKER = 8, 9            # kernel ids of fault records only
@@ -248,6 +251,7 @@ _PROTOS = {
                                               ctypes.c_uint16]),
     "yrss_set_kni": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.c_char_p]),
+    "yrss_set_extended": (ctypes.c_int, [_vp, _u32]),
     "yrss_dispatch_dev_ex": (ctypes.c_int, [_vp, ctypes.POINTER(DevBatch), _vp]),
     "yrss_dispatch_dev_seg": (ctypes.c_int, [_vp, ctypes.POINTER(DevSegBatch), _vp]),
     "yrss_seg_to_lists": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
@@ -281,7 +285,8 @@ _PROTOS = {
 # entry points of the segmented list form (absent from older builds, see load())
 _SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists", "yrss_route_dev_seg",
               "yrss_route_seg", "yrss_worker_start_route", "yrss_route_lists_burst",
-              "yrss_route_lists_frames", "yrss_route_lists")
+              "yrss_route_lists_frames", "yrss_route_lists",
+              "yrss_set_extended")   # (and the extended mode after them)
 
 # include/yrss_test_hooks.h (libyrss_test.so)
 _TEST_PROTOS = {

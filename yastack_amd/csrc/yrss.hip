@@ -80,6 +80,14 @@ constexpr int kRsrcWord3 = 0x00020000;  // buffer resource dword 3 for gfx9-fami
 constexpr uint32_t kOutTiles = 4;       // parse: output burst (tiles buffered in LDS)
 constexpr int kOutBytes = kOutTiles * kTile * (4 + 2 + 1 + 2);   // hash, q, filter, rank
 constexpr int kStageBytes = kTile * 64; // 4 KiB per wave
+// Extended mode (yrss_set_extended; the build's own semantics, not fs/lib's):
+// the IPv6 tuple is 36 bytes, 288 key windows.  Its tables are nibble tables,
+// 72 x 16 words = 4.5 KiB (36 byte tables are 36 KiB and do not fit beside the
+// KNI bitmaps), 72 lookups a hashed IPv6 packet, each table inside 16 banks.
+constexpr int kExtTupleBytes = 36;
+constexpr int kExtWins = 8 * kExtTupleBytes;          // 288
+constexpr int kExtTblWords = 2 * kExtTupleBytes * 16; // 1152
+constexpr int kExtTblBytes = kExtTblWords * 4;
 
 // Everything yrss_parse_hash needs, passed by value (kernarg segment).
 struct ParseParams {
@@ -116,6 +124,9 @@ struct ParseParams {
     uint32_t *rbin;       // with tot_acc: [nb][kLbMaxWgs] counts per line-scatter range
     uint32_t rbin_chunks; // chunks a range (a multiple of 8)
     uint32_t kwin[96];    // key window at every tuple bit position
+    uint32_t ext;         // kExt kernels: YRSS_EXT_* (yrss_set_extended); their 288 key
+                          // windows follow the KNI bitmaps at kni_bm + kKniWords
+                          // (the word sits in what was padding, like route_lq)
     uint8_t *seg_idx;     // kCount == 3: per 256-packet segment, its packets' segment-local
                           // indices grouped by bucket (yrss_dispatch_dev_seg)
     uint16_t *seg_off;    // kCount == 3: [segments][nb + 1] bucket offsets inside a segment
@@ -494,11 +505,153 @@ __device__ __forceinline__ void flush_seg(const ParseParams &P, const uint16_t *
     wave_lds_sync();
 }
 
-template <int kCount, bool kFilter>
+// ---- extended mode (yrss_set_extended): the build's own semantics -----------
+// Nibble table m (0..71), value v: XOR of the key windows xwin[4m + b] over v's
+// set bits b (b = 0 is the nibble's most significant bit).  xwin: 288 windows
+// in device memory.  Threads tid, tid + nthr, ...
+__device__ __forceinline__ void build_ext_tables(uint32_t *xtbl, const uint32_t *xwin,
+                                                 uint32_t tid, uint32_t nthr)
+{
+    for (uint32_t e = tid; e < (uint32_t)kExtTblWords; e += nthr) {
+        const uint32_t m = e >> 4, v = e & 0xfu;
+        uint32_t acc = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            acc ^= (v & (0x8u >> b)) ? xwin[4 * m + b] : 0u;
+        xtbl[e] = acc;
+    }
+}
+
+// Toeplitz over tuple word k (wire order, first byte on top): eight lookups
+// into nibble tables 8k .. 8k + 7.
+__device__ __forceinline__ uint32_t tz_nib(uint32_t w, const uint32_t *xt)
+{
+    uint32_t h = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        h ^= xt[16 * i + ((w >> (28 - 4 * i)) & 0xfu)];
+    return h;
+}
+
+// The packet's queue and hash under P.ext (include/yrss.h, "extended mode").
+//   YRSS_EXT_VLAN  up to two tags (0x8100 / 0x88A8 outside, 0x8100 inside) are
+//                  skipped: L3 at o = 14 + 4t, and every length rule of the
+//                  reference sees len - 4t (a frame too short for its tags
+//                  and the inner ethertype stays unhashed)
+//   IPv4           the reference's rule (ff_dpdk_if.c:1968-2035) at offset o;
+//                  with YRSS_EXT_UDP protocol 17 hashes like TCP
+//   YRSS_EXT_IPV6  next-header 6 (17 with YRSS_EXT_UDP), len - o >= 44: the 36
+//                  wire-order bytes src | dst | sport | dport
+// o is a whole number of dwords past 14, so every field of the untagged parse
+// is the same bytes of a dword t further on.  Dwords past the staged 64 bytes
+// come from HBM while they lie inside the window (4 i + 4 <= stride, and the
+// stride is a multiple of 16); ports that end beyond it give YRSS_Q_TRUNCATED.
+struct ExtResult {
+    int q;
+    uint32_t h;
+};
+
+__device__ __forceinline__ ExtResult ext_classify(const ParseParams &P, const uint32_t *tbl,
+                                                  const uint32_t *xtbl, const uint32_t *mine,
+                                                  uint32_t rsw, uint32_t pkt, bool valid,
+                                                  uint32_t L)
+{
+    auto dw = [&](uint32_t i) {   // dword i < 16 of this lane's staged window
+        return mine[(((i >> 2) ^ rsw) << 2) | (i & 3u)];
+    };
+    auto et_of = [](uint32_t d) { return ((d & 0xffu) << 8) | ((d >> 8) & 0xffu); };
+    const bool eth = valid && L >= 14u;
+    uint32_t t = 0, et = et_of(dw(3));
+    bool ok = eth;
+    if ((P.ext & YRSS_EXT_VLAN) && eth && (et == 0x8100u || et == 0x88A8u)) {
+        t = 1u;
+        et = et_of(dw(4));
+        ok = L >= 18u;
+        if (ok && et == 0x8100u) {
+            t = 2u;
+            et = et_of(dw(5));
+            ok = L >= 22u;
+        }
+    }
+    const uint32_t Ls = L - 4u * t;   // the stripped frame's length; L3 at o = 14 + 4t <= L
+    int qv = ok && (et == 0x0806u || et == 0x8035u) ? 0 : YRSS_DEFAULT_Q;
+    uint32_t h = 0;
+    const uint32_t g5 = dw(5u + t);   // IPv4: protocol on top; IPv6: next-header at the bottom
+    const bool udp = (P.ext & YRSS_EXT_UDP) != 0u;
+    bool hashed = false, trunc = false;
+    if (ok && et == 0x0800u) {
+        const uint32_t ihl = (dw(3u + t) >> 16) & 0xfu, ihl4 = ihl << 2;
+        const uint32_t proto = g5 >> 24;
+        hashed = Ls - 14u >= 20u && Ls - 14u >= ihl4 && Ls - ihl4 >= 20u &&
+                 (proto == 6u || (udp && proto == 17u));
+        if (hashed) {
+            const uint32_t d6 = dw(6u + t), d7 = dw(7u + t), d8 = dw(8u + t);
+            const uint32_t w0 = __builtin_amdgcn_alignbit(d7, d6, 16);
+            const uint32_t w1 = __builtin_amdgcn_alignbit(d8, d7, 16);
+            // ports at byte o + 4 IHL: dwords j (bytes 2, 3) and j + 1 (bytes
+            // 0, 1); the slow path is keyed on where they land
+            const uint32_t j = 3u + t + ihl;
+            uint32_t pa = 0, pb = 0;
+            if (__builtin_expect(j + 1u < 16u, 1)) {
+                pa = dw(j);
+                pb = dw(j + 1u);
+            } else if (4u * j + 6u <= P.stride) {
+                const uint32_t *g =
+                    reinterpret_cast<const uint32_t *>(P.win + (size_t)pkt * P.stride);
+                pa = __builtin_nontemporal_load(g + j);
+                pb = __builtin_nontemporal_load(g + j + 1u);
+            } else {
+                trunc = true;
+            }
+            h = tz_lds(w0, tbl) ^ tz_lds(w1, tbl + kTblWordsPerTupleWord) ^
+                tz_lds((pa & 0xffff0000u) | (pb & 0xffffu), tbl + 2 * kTblWordsPerTupleWord);
+        }
+    } else if (ok && et == 0x86DDu && (P.ext & YRSS_EXT_IPV6)) {
+        const uint32_t nh = g5 & 0xffu;   // byte o + 6
+        hashed = Ls - 14u >= 44u && (nh == 6u || (udp && nh == 17u));
+        if (hashed) {
+            // tuple bytes o + 8 .. o + 43: the top half of dword 5 + t, dwords
+            // 6 + t .. 13 + t, the bottom half of dword 14 + t (dword 16 with
+            // two tags: bytes 64..67)
+            uint32_t last = 0;
+            if (14u + t < 16u)
+                last = dw(14u + t);
+            else if (P.stride >= 68u)
+                last = __builtin_nontemporal_load(
+                    reinterpret_cast<const uint32_t *>(P.win + (size_t)pkt * P.stride) + 16);
+            else
+                trunc = true;
+            uint32_t lo = g5;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const uint32_t hi = k < 8 ? dw(6u + t + (uint32_t)k) : last;
+                const uint32_t w = __builtin_bswap32(__builtin_amdgcn_alignbit(hi, lo, 16));
+                h ^= tz_nib(w, xtbl + 128 * k);
+                lo = hi;
+            }
+        }
+    }
+    if (hashed) {
+        const uint32_t rem = (P.mod_d & (P.mod_d - 1u)) == 0u
+                                 ? h & (P.mod_d - 1u)
+                                 : (uint32_t)__umul64hi(P.mod_m * (uint64_t)h, (uint64_t)P.mod_d);
+        qv = (int)(uint16_t)(rem + P.q_off);
+        if (trunc) {
+            qv = YRSS_Q_TRUNCATED;
+            h = 0u;
+        }
+    }
+    return ExtResult{qv, h};
+}
+
+// kExt: queue and hash by ext_classify (xtbl: its nibble tables); the
+// protocol_filter class still follows the reference on the unstripped frame.
+template <int kCount, bool kFilter, bool kExt = false>
 __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_t *tbl,
                                              const uint32_t *kni, u32x4 *stage, uint32_t *cnt,
                                              const OutSlot &ob, uint32_t t0, uint32_t end,
-                                             uint32_t lane, const u32x4 (&r)[4], uint32_t Lraw)
+                                             uint32_t lane, const u32x4 (&r)[4], uint32_t Lraw,
+                                             const uint32_t *xtbl = nullptr)
 {
     // Staging layout: chunk c (16 B) of tile packet p at slot p*4 + (c ^ ((p>>2)&3)).
     // Writes: lane l holds chunk l&3 of packet 16k + l/4, so (p>>2)&3 == (l>>4)&3.
@@ -542,10 +695,15 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
     const bool eth = valid && L >= 14u;
     const bool ip_ok = eth && et == 0x0800u && L - 14u >= 20u && L - 14u >= ihl4;
     int qv = YRSS_DEFAULT_Q;
-    if (eth && (et == 0x0806u || et == 0x8035u))
+    if (!kExt && eth && (et == 0x0806u || et == 0x8035u))
         qv = 0;
-    const bool hashed = ip_ok && (L - ihl4) >= 20u && proto == 6u;
+    const bool hashed = !kExt && ip_ok && (L - ihl4) >= 20u && proto == 6u;
     uint32_t h = 0;
+    if (kExt) {
+        const ExtResult x = ext_classify(P, tbl, xtbl, mine, rsw, pkt, valid, L);
+        qv = x.q;
+        h = x.h;
+    }
     if (hashed) {
         // Tuple = LE image of ntohl(src), ntohl(dst), ntohs(sport), ntohs(dport)
         // (ff_dpdk_if.c:1994-2021).
@@ -662,12 +820,14 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
 //            the class is computed even when no filter output is asked for
 //   kFilter  also classify protocol_filter / KNI (one byte per packet)
 //   kBlock   workgroup size (256/512): waves per CU, one key table per group
+//   kExt     extended mode (ext_classify): 4.5 KiB of nibble tables after the
+//            KNI bitmaps; the other variants are the code they were without it
 // Window loads are non-temporal (streaming): ~25 % faster than default-policy
 // loads (profiles/r01_v32_nt_ab.log).
 // LDS: key tables 12 KiB | staging 4 KiB per wave | count slots 8 KiB per wave |
 //      output buffer 2.25 KiB per wave | KNI bitmaps 16 KiB (kFilter only).
 // ---------------------------------------------------------------------------
-template <int kCount, bool kFilter, int kBlock>
+template <int kCount, bool kFilter, int kBlock, bool kExt = false>
 __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
 {
     constexpr int kWaves = kBlock / kWave;
@@ -686,11 +846,14 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
     uint16_t *orank = reinterpret_cast<uint16_t *>(out_w + kOutTiles * kTile * 7);
     uint32_t *kni = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(cnt_base) +
                                                  kWaves * (kCntWords * 4 + kOutBytes));
+    uint32_t *xtbl = kni + (kFilter ? kKniWords : 0);   // kExt only
 
     const uint32_t gw = blockIdx.x * kWaves + wave;
     const uint32_t W = gridDim.x * kWaves;
 
     build_key_tables(tbl, P.kwin, threadIdx.x, kBlock);
+    if (kExt)
+        build_ext_tables(xtbl, P.kni_bm + kKniWords, threadIdx.x, kBlock);
     if (kFilter)
         for (uint32_t e = threadIdx.x; e < (uint32_t)kKniWords; e += kBlock)
             kni[e] = P.kni_enable ? P.kni_bm[e] : 0u;
@@ -765,15 +928,15 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
         for (uint32_t i = 0;; i += 2) {
             const bool hB = tile_at(i + 1, tB, sB);
             load_tile<true>(P, hB ? tB : tA, P.n, lane, rB, LB);
-            process_tile<kC, kFilter>(P, tbl, kni, stage, cnt_w + sA * P.nb, slot(i), tA, P.n,
-                                      lane, rA, LA);
+            process_tile<kC, kFilter, kExt>(P, tbl, kni, stage, cnt_w + sA * P.nb, slot(i), tA,
+                                            P.n, lane, rA, LA, xtbl);
             after(i, tA, !hB);
             if (!hB)
                 break;
             const bool hA = tile_at(i + 2, tA, sA);
             load_tile<true>(P, hA ? tA : tB, P.n, lane, rA, LA);
-            process_tile<kC, kFilter>(P, tbl, kni, stage, cnt_w + sB * P.nb, slot(i + 1), tB,
-                                      P.n, lane, rB, LB);
+            process_tile<kC, kFilter, kExt>(P, tbl, kni, stage, cnt_w + sB * P.nb, slot(i + 1),
+                                            tB, P.n, lane, rB, LB, xtbl);
             after(i + 1, tB, !hA);
             if (!hA)
                 break;
@@ -2567,12 +2730,14 @@ struct SmallParams {
     uint64_t seq;        // stored into *done once every output is visible to the host
 };
 
-__host__ __device__ constexpr size_t small_lds(uint32_t nb, bool filter)
+__host__ __device__ constexpr size_t small_lds(uint32_t nb, bool filter, bool ext = false)
 {
     return kTblBytes + kSmallWaves * (kStageBytes + kOutBytes) +
            (size_t)(kSmallTiles * nb + kSmallMaxNb) * sizeof(uint32_t) +
-           (filter ? kKniWords * sizeof(uint32_t) : 0u);
+           (filter ? kKniWords * sizeof(uint32_t) : 0u) + (ext ? kExtTblBytes : 0u);
 }
+static_assert(small_lds(kSmallMaxNb, true, true) <= 160u * 1024u,
+              "the extended one-launch kernel's LDS at the most buckets fits one CU");
 
 // LDS carve-up shared by the one-shot kernel and the worker.
 struct SmallLds {
@@ -2633,7 +2798,7 @@ struct BurstIO {
 // global (one start row, 32-bit indices): no segment, so the only limit is one
 // lane per class, nq + 3 <= 64.
 template <bool kFilter, uint32_t kTW = kOutTiles,   // kTW: tiles per wave (n <= kTW * 1024)
-          bool kRoute = false>
+          bool kRoute = false, bool kExt = false>
 __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, const GatherIO &gio,
                                  const BurstIO &S, const SmallLds &L, uint32_t wave,
                                  uint32_t lane)
@@ -2665,10 +2830,10 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
             break;
         static_assert(!kRoute || kFilter, "route classes need the filter class");
         // (kCount 4 is kCount 2 without the rank tag, over route_bucket)
-        process_tile<kRoute ? 4 : 2, kFilter>(P, L.tbl, L.kni, L.stage, L.cnt + t * P.nb,
-                                 OutSlot{L.oq + j * kTile, L.oh + j * kTile, L.of + j * kTile,
-                                         L.orank + j * kTile},
-                                 t * kTile, P.n, lane, r[j], Ln[j]);
+        process_tile<kRoute ? 4 : 2, kFilter, kExt>(
+            P, L.tbl, L.kni, L.stage, L.cnt + t * P.nb,
+            OutSlot{L.oq + j * kTile, L.oh + j * kTile, L.of + j * kTile, L.orank + j * kTile},
+            t * kTile, P.n, lane, r[j], Ln[j], L.kni + (kFilter ? kKniWords : 0));
     }
     __syncthreads();
     // per bucket: exclusive prefix over the tiles (in place) and the total
@@ -2726,16 +2891,21 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
     }
 }
 
-template <bool kFilter, bool kRoute = false>
+// kExt: extended mode (ext_classify), its nibble tables after the KNI bitmaps
+// (after the start row without them).
+template <bool kFilter, bool kRoute = false, bool kExt = false>
 __global__ __launch_bounds__(kSmallBlock) void yrss_burst_small(SmallParams S)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const SmallLds L = small_carve(smem, wave, S.P.nb);
     small_tables<kFilter>(S.P, L);
-    small_burst_body<kFilter, kOutTiles, kRoute>(S.P, S.G, gather_io(S.G),
-                                                 BurstIO{S.qidx, S.qstart, S.gather, S.writeback},
-                                                 L, wave, lane_id());
+    if (kExt)
+        build_ext_tables(L.kni + (kFilter ? kKniWords : 0), S.P.kni_bm + kKniWords, threadIdx.x,
+                         kSmallBlock);
+    small_burst_body<kFilter, kOutTiles, kRoute, kExt>(
+        S.P, S.G, gather_io(S.G), BurstIO{S.qidx, S.qstart, S.gather, S.writeback}, L, wave,
+        lane_id());
     if (S.done) {
         // the host spins on this word instead of a stream synchronisation:
         // every wave's stores drained, one system-scope release, then the word
@@ -3205,6 +3375,7 @@ struct yrss_ctx {
     bool kni_enable = false;
     bool kni_accept = false;
     uint8_t kni_bm[2 * 8192] = {};   // tcp bitmap then udp bitmap, htons-indexed
+    uint32_t ext = 0;                // YRSS_EXT_* (yrss_set_extended); 0: the reference's rules
     struct Occ {
         const void *fn;
         uint32_t block, lds, blocks;
@@ -3230,7 +3401,7 @@ struct yrss_ctx {
     // what lives as long as the context
     BufOwner own;
     PinnedBuf<uint32_t> fault_rec;  // host-coherent fault record {code, kernel, where, value}
-    DevBuf<uint32_t> kni;
+    DevBuf<uint32_t> kni;           // the KNI bitmaps, then the 288 extended key windows
     Staged<uint32_t> fault;         // zero-copy gather fault word (h host-coherent)
     PinnedBuf<uint64_t> done;       // host-coherent completion word of yrss_burst_small
     uint64_t done_seq = 0;
@@ -3323,12 +3494,14 @@ namespace {
 
 constexpr uint32_t kParseBlock = 512;   // 8 waves: one workgroup per CU (LDS)
 
-size_t parse_lds(bool filter)
+constexpr size_t parse_lds(bool filter, bool ext = false)
 {
     constexpr size_t w = kParseBlock / kWave;
     return kTblBytes + w * kStageBytes + w * (kCntWords * sizeof(uint32_t) + kOutBytes) +
-           (filter ? kKniWords * sizeof(uint32_t) : 0u);
+           (filter ? kKniWords * sizeof(uint32_t) : 0u) + (ext ? kExtTblBytes : 0u);
 }
+static_assert(parse_lds(true, true) <= 160u * 1024u,
+              "the extended filter variant's LDS (150.5 KiB) fits one CU");
 
 // One workgroup per CU (the LDS of the filter variant admits no second), so
 // the grid does not depend on whether the filter is on and a batch's layout
@@ -3477,8 +3650,28 @@ typedef void (*ParseKernel)(ParseParams);
 // count: 0 none, 1 per-chunk counts, 2 counts + per-packet chunk ranks,
 // 3 segmented lists (yrss_dispatch_dev_seg only), 4 segmented lists over route
 // classes (yrss_route_dev_seg only; always with the filter class)
-ParseKernel pick_parse(int count, bool filter)
+// ext: the extended-mode instantiations (yrss_set_extended)
+template <bool kExt>
+ParseKernel pick_parse_of(int count, bool filter)
 {
+    if (count == 4)
+        return yrss_parse_hash<4, true, kParseBlock, kExt>;
+    if (count == 3)
+        return filter ? yrss_parse_hash<3, true, kParseBlock, kExt>
+                      : yrss_parse_hash<3, false, kParseBlock, kExt>;
+    if (filter)
+        return count == 2 ? yrss_parse_hash<2, true, kParseBlock, kExt>
+               : count    ? yrss_parse_hash<1, true, kParseBlock, kExt>
+                          : yrss_parse_hash<0, true, kParseBlock, kExt>;
+    return count == 2 ? yrss_parse_hash<2, false, kParseBlock, kExt>
+           : count    ? yrss_parse_hash<1, false, kParseBlock, kExt>
+                      : yrss_parse_hash<0, false, kParseBlock, kExt>;
+}
+
+ParseKernel pick_parse(int count, bool filter, bool ext)
+{
+    if (ext)
+        return pick_parse_of<true>(count, filter);
     if (count == 4)
         return yrss_parse_hash<4, true, kParseBlock>;
     if (count == 3)
@@ -3509,6 +3702,7 @@ ParseParams parse_params(const yrss_ctx *c, int route_lq, bool out16)
     P.fault = c->fault_rec.dh;
     P.kni_bm = c->kni.d;
     P.kni_enable = c->kni_enable ? 1u : 0u;
+    P.ext = c->ext;
     P.out16 = out16 ? 1u : 0u;
     if (route_lq >= 0) {
         P.nb = c->nb + 2u;
@@ -3560,9 +3754,12 @@ struct Timed {
     }
 };
 
-void compute_key_schedule(const yrss_config *cfg, uint32_t kwin[96])
+// kwin[k]: the 32 key bits from bit k on; bits past rss_key_len count as zero,
+// as in toeplitz_hash (ff_dpdk_if.c:1896).  96 windows for the reference's
+// 12-byte tuple, kExtWins for the extended mode's 36 bytes.
+void compute_key_schedule(const yrss_config *cfg, uint32_t *kwin, unsigned nwin = 96)
 {
-    for (unsigned k = 0; k < 96; ++k) {
+    for (unsigned k = 0; k < nwin; ++k) {
         uint32_t w = 0;
         for (unsigned b = 0; b < 32; ++b) {
             const unsigned bit = k + b, kb = bit >> 3;
@@ -3817,9 +4014,19 @@ int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = tru
     } else {
         S.done = nullptr;
     }
-    const size_t lds = small_lds(S.P.nb, filter || route);
+    const size_t lds = small_lds(S.P.nb, filter || route, S.P.ext != 0u);
     const dim3 grid(1);
-    if (route)
+    if (S.P.ext) {
+        if (route)
+            hipLaunchKernelGGL((yrss_burst_small<true, true, true>), grid, dim3(kSmallBlock), lds,
+                               stream, S);
+        else if (filter)
+            hipLaunchKernelGGL((yrss_burst_small<true, false, true>), grid, dim3(kSmallBlock),
+                               lds, stream, S);
+        else
+            hipLaunchKernelGGL((yrss_burst_small<false, false, true>), grid, dim3(kSmallBlock),
+                               lds, stream, S);
+    } else if (route)
         hipLaunchKernelGGL((yrss_burst_small<true, true>), grid, dim3(kSmallBlock), lds, stream, S);
     else if (filter)
         hipLaunchKernelGGL(yrss_burst_small<true>, grid, dim3(kSmallBlock), lds, stream, S);
@@ -4212,14 +4419,19 @@ int yrss_init(const struct yrss_config *cfg, yrss_ctx **out)
     c->proto.nq = cfg->nb_queues;
     c->proto.nb = c->nb;   // (every other field stays zero: parse_params)
 
+    static_assert(sizeof(c->kni_bm) == kKniWords * sizeof(uint32_t), "the bitmaps, then the windows");
+    uint32_t xwin[kExtWins];
+    compute_key_schedule(cfg, xwin, kExtWins);
     hipError_t e;
     if ((e = list_ws_alloc(c, c->ws)) != hipSuccess ||
         (e = c->fault_rec.alloc(c->own, 16, hipHostMallocCoherent)) != hipSuccess ||   // 64 B
-        (e = c->kni.alloc(c->own, sizeof(c->kni_bm) / sizeof(uint32_t))) != hipSuccess ||
+        (e = c->kni.alloc(c->own, kKniWords + kExtWins)) != hipSuccess ||
         (e = c->fault.alloc(c->own, 1)) != hipSuccess ||
         (e = c->fault.alloc(c->own, 1, hipHostMallocCoherent)) != hipSuccess ||
         (e = c->done.alloc(c->own, 8, hipHostMallocCoherent)) != hipSuccess ||        // 64 B
         (e = hipMemset(c->kni.d, 0, sizeof(c->kni_bm))) != hipSuccess ||
+        (e = hipMemcpy(c->kni.d + kKniWords, xwin, sizeof(xwin), hipMemcpyHostToDevice)) !=
+            hipSuccess ||
         (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming)) != hipSuccess) {
         yrss_fini(c);
@@ -4336,6 +4548,26 @@ int yrss_set_kni(yrss_ctx *c, int enable, const char *method, const char *tcp_po
     YRSS_HIP(hipSetDevice(c->device));
     YRSS_HIP(hipMemcpy(c->kni.d, c->kni_bm, sizeof(c->kni_bm), hipMemcpyHostToDevice));
     YRSS_HIP(hipDeviceSynchronize());   // ordered before any stream's next dispatch
+    return 0;
+}
+
+int yrss_set_extended(yrss_ctx *c, uint32_t flags)
+{
+    if (!c || (flags & ~(uint32_t)YRSS_EXT_ALL))
+        return -EINVAL;
+    if (c->pend.active)   // the burst in flight was queued under the old flags
+        return -EBUSY;
+    if (c->w.on) {
+        // a resident worker serves the reference's rules only: it is halted
+        // here and its submits are refused while flags are set
+        if (c->w.pending)
+            return -EBUSY;
+        YRSS_HIP(hipSetDevice(c->device));
+        const int hrc = worker_halt(c);
+        if (hrc)
+            return hrc;
+    }
+    c->ext = flags;   // a launch argument (parse_params): nothing to upload
     return 0;
 }
 
@@ -4526,9 +4758,9 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     P.rbin_chunks = fused ? rcs << lp.gshift : 0u;
     {
         Timed t(c, YRSS_K_PARSE_HASH);
-        hipExtLaunchKernelGGL(pick_parse(ranked ? 2 : compact ? 1 : 0, filter), dim3(grid),
-                              dim3(kParseBlock),
-                              (uint32_t)parse_lds(filter), s, t.a, t.b, 0, P);
+        hipExtLaunchKernelGGL(pick_parse(ranked ? 2 : compact ? 1 : 0, filter, c->ext != 0u),
+                              dim3(grid), dim3(kParseBlock),
+                              (uint32_t)parse_lds(filter, c->ext != 0u), s, t.a, t.b, 0, P);
     }
     YRSS_HIP(hipGetLastError());
     if (fused)
@@ -4702,8 +4934,9 @@ static int dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, bool route,
     P.seg_off = b->seg_off;
     {
         Timed t(c, YRSS_K_PARSE_HASH);
-        hipExtLaunchKernelGGL(pick_parse(route ? 4 : 3, filter), dim3(grid_for(c, n)),
-                              dim3(kParseBlock), (uint32_t)parse_lds(filter), s, t.a, t.b, 0, P);
+        hipExtLaunchKernelGGL(pick_parse(route ? 4 : 3, filter, c->ext != 0u),
+                              dim3(grid_for(c, n)), dim3(kParseBlock),
+                              (uint32_t)parse_lds(filter, c->ext != 0u), s, t.a, t.b, 0, P);
     }
     YRSS_HIP(hipGetLastError());
     return 0;
@@ -5244,6 +5477,8 @@ int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uin
         return -EINVAL;
     if (route && c->cfg.nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
         return -ENOTSUP;
+    if (c->ext)   // the worker kernel has no extended variant (yrss_set_extended)
+        return -ENOTSUP;
     if (c->w.on)
         return -EBUSY;
     YRSS_HIP(hipSetDevice(c->device));
@@ -5328,6 +5563,8 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     auto &w = c->w;
     if (!w.on)
         return -ENODEV;
+    if (c->ext)   // refused, not served by the reference's rules (yrss_set_extended)
+        return -ENOTSUP;
     if (n > kWorkerMaxBurst)
         return -E2BIG;
     const uint64_t t = w.issued + 1u;

@@ -253,6 +253,19 @@ class SoftRss:
                                          enc(tcp_ports), enc(udp_ports)), "yrss_set_kni")
         self._kni_enable = bool(enable)
 
+    # -- extended mode (this build's own semantics, not fs/lib's) -----------
+    def set_extended(self, vlan: bool = False, ipv6: bool = False, udp: bool = False) -> None:
+        """Opt into hashing what ``toeplitz_dispatch`` leaves on queue 2
+        (``yrss_set_extended``): ``vlan`` classifies a frame as if its one or
+        two VLAN tags had been stripped, ``ipv6`` hashes IPv6 TCP over the 36
+        wire-order tuple bytes, ``udp`` lets UDP take the TCP branch.  All
+        False restores the reference's rules exactly.  The persistent worker
+        refuses bursts (ENOTSUP) while any flag is set."""
+        flags = (abi.EXT_VLAN if vlan else 0) | (abi.EXT_IPV6 if ipv6 else 0) | \
+            (abi.EXT_UDP if udp else 0)
+        abi.check(self._lib.yrss_set_extended(self._ctx, flags), "yrss_set_extended")
+        self.ext_flags = flags
+
     # -- device-resident path ---------------------------------------------
     def dispatch_dev(self, win, lens, stride: int, n: int | None = None, *,
                      out=None, want_hash: bool = True, compact: bool = True,

@@ -226,15 +226,23 @@ int yrss_set_kni(yrss_ctx *ctx, int enable, const char *method,
  *
  * Honoured by every yrss_dispatch_dev*, yrss_route_dev_seg, the host bursts
  * and frames (zero-copy and routed forms included) and by
- * yrss_toeplitz_dispatch on a context without a worker.  NOT by the
- * persistent worker: while flags are set yrss_worker_start*, every
- * yrss_worker_submit* and so the shim on a worker context are refused
- * (-ENOTSUP; the shim returns -1).  The helper process and the fan-out own
- * their contexts and stay on the reference's rules.
+ * yrss_toeplitz_dispatch on a context without a worker.  The persistent
+ * worker honours them when it was started to:
+ * yrss_worker_start_flags(..., YRSS_WORKER_F_EXTENDED) serves every
+ * yrss_worker_submit* (and the shim's one-packet bursts) under the flags in
+ * force at the submit; in the windows form the caller's stride sets the
+ * window rule above.  A worker started by yrss_worker_start or
+ * yrss_worker_start_route serves the reference's rules only and says so by
+ * refusing: while flags are set those two calls, every yrss_worker_submit* on
+ * such a worker and so the shim on its context return -ENOTSUP (the shim -1).
+ * The helper process (yrss_remote_set_extended) and the fan-out
+ * (yrss_fanout_set_extended) own their contexts and set the flags on them.
  *
  * flags == 0 restores the reference's rules exactly.  -EINVAL on unknown
  * bits; -EBUSY while a YRSS_F_ASYNC or worker burst is pending; a resident
- * worker is halted (the next submit after flags return to 0 relaunches it). */
+ * worker is halted, and the next submit it serves relaunches it: under the new
+ * flags for a YRSS_WORKER_F_EXTENDED worker, after the flags return to 0 for
+ * any other.  Tickets continue across the relaunch. */
 #define YRSS_EXT_VLAN 0x1u
 #define YRSS_EXT_IPV6 0x2u
 #define YRSS_EXT_UDP  0x4u
@@ -711,6 +719,20 @@ int yrss_worker_start(yrss_ctx *ctx, uint32_t nslots, uint32_t nblocks);
  * otherwise halts the kernel, so the next submit relaunches it with the new
  * state (as registering host memory does). */
 int yrss_worker_start_route(yrss_ctx *ctx, uint32_t nslots, uint32_t nblocks, uint16_t queue_id);
+/* The worker with its options spelled out: flags 0 is yrss_worker_start,
+ * YRSS_WORKER_F_ROUTE is yrss_worker_start_route (queue_id is read only then).
+ * YRSS_WORKER_F_EXTENDED makes the worker follow yrss_set_extended: it starts
+ * whatever the context's flags are, and each launch of its kernel serves the
+ * flags the context holds then (the extended kernel, with 4.5 KiB more LDS for
+ * its nibble tables, while any flag is set; with flags 0 the very kernel of
+ * yrss_worker_start[_route]).  yrss_set_extended halts it as it halts any
+ * worker; its next submit relaunches it.  In route mode the lists follow the
+ * extended q, and the filter class the reference on the unstripped frame.
+ * -EINVAL on unknown bits; otherwise as the two calls above. */
+#define YRSS_WORKER_F_ROUTE    0x1u   /* as yrss_worker_start_route (queue_id is read) */
+#define YRSS_WORKER_F_EXTENDED 0x2u   /* the worker follows yrss_set_extended */
+int yrss_worker_start_flags(yrss_ctx *ctx, uint32_t nslots, uint32_t nblocks,
+                            uint32_t flags, uint16_t queue_id);
 /* Queue one burst (n <= YRSS_WORKER_MAX_BURST; flags: YRSS_F_WRITE_RSS);
  * *ticket identifies it for yrss_worker_poll.  The output arrays must stay
  * valid until the ticket is polled. */
@@ -764,6 +786,11 @@ int yrss_fanout_init(const struct yrss_config *cfg, const int *devices, uint32_t
                      uint32_t nslots, uint32_t nblocks, yrss_fanout **out);
 int yrss_fanout_fini(yrss_fanout *f);
 uint32_t yrss_fanout_size(yrss_fanout *f);
+/* yrss_set_extended on every context of the fan-out (their workers are started
+ * with YRSS_WORKER_F_EXTENDED).  -EINVAL on unknown bits; -EBUSY while a ticket
+ * is outstanding (submitted and not yet returned by yrss_fanout_next); if a
+ * context refuses, those already changed are set back and its error returned. */
+int yrss_fanout_set_extended(yrss_fanout *f, uint32_t flags);
 int yrss_fanout_register_host_memory(yrss_fanout *f, void *base, size_t len);
 int yrss_fanout_unregister_host_memory(yrss_fanout *f, void *base);
 /* As yrss_worker_submit / yrss_worker_submit_frames; *ticket is the fan-out's. */

@@ -32,6 +32,8 @@
  * Results are bit-identical to yrss_worker_submit_frames (toeplitz_dispatch,
  * ff_dpdk_if.c:1945-2113, and the process_packets FIFO lists, :1058-1094).
  * One client per lcore thread; calls of one client come from one thread.
+ * (The opt-in extended mode of yrss_set_extended, which is not the
+ * reference's, is in yrss_remote_ext.h.)
  */
 #ifndef YRSS_REMOTE_H
 #define YRSS_REMOTE_H

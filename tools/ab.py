@@ -17,6 +17,11 @@ path, relative to the repository root or absolute (tools/build_ab_lib.sh).
 k=v: yrss_set_tuning fields, side=1 (the batches on a non-default stream),
 ext=N (yrss_set_extended flags: 1 VLAN, 2 IPv6, 4 UDP), dbg_groups / dbg_merge (the test library's hooks); dev legs only.  form, dev:
 global (default), seg, seg-filter, route; worker: plain (default), route.
+A worker leg takes two keys of its own: ext=N starts the worker with
+YRSS_WORKER_F_EXTENDED under flags N (ext=0: that worker with the flags off;
+no ext: yrss_worker_start[_route], all an older library has), prof=N takes the
+frames from synthetic profile N (abi.SYN_*: 1 udp4, 3 vlan6_tcp, 5 tcp4; default
+6, the fuzz stream).
 
 dev times --steps back-to-back batches by wall clock (step, ms, no events) and,
 in a separate block, the form's kernels by events (us; a kernel the
@@ -223,14 +228,14 @@ def main_dev(args):
 
 # ---- worker legs -------------------------------------------------------------
 
-def make_pool(n):
+def make_pool(n, profile=abi.SYN_FUZZ):
     """n synthetic frames (SYN_FUZZ: TCP, UDP, ARP, IPIP) at 2048-byte pitch
     in page-aligned memory: (memory, data pointers, data_len)."""
     import numpy as np
 
     from oracle import oracle
 
-    win, lens = oracle.synth(abi.SYN_FUZZ, n, 7, stride=80)
+    win, lens = oracle.synth(profile, n, 7, stride=80)
     lens = np.minimum(lens, 1500).astype(np.uint16)
     raw = np.zeros(n * 2048 + 8192, np.uint8)
     mem = raw[(-raw.ctypes.data) % 4096:][:n * 2048]
@@ -243,11 +248,15 @@ def run_worker_leg(leg, args, burst, mem, data, lens):
     import numpy as np
 
     npr = args.nb_procs
+    ext = leg.tune.get("ext")
     with SoftRss(npr, npr, 1, 1, device=0, max_burst=0, lib_path=lib_path(leg.lib)) as e:
         e.set_kni(*KNI)
         e.register_host_memory(mem.ctypes.data, mem.nbytes)
+        if ext:
+            e.set_extended(vlan=bool(ext & 1), ipv6=bool(ext & 2), udp=bool(ext & 4))
         e.worker_start(args.nslots, args.nblocks,
-                       route_queue_id=args.queue_id if leg.form == "route" else None)
+                       route_queue_id=args.queue_id if leg.form == "route" else None,
+                       **({} if ext is None else {"extended": True}))
         lib, ctx = e._lib, e._ctx
         nslot = args.nslots
         outs = [(np.empty(burst, np.int16), np.empty(burst, np.uint32),
@@ -289,11 +298,13 @@ def run_worker_leg(leg, args, burst, mem, data, lens):
 
 def main_worker(args):
     rng = random.Random(args.seed)
-    pool = make_pool(8192)
+    pools = {p: make_pool(8192, p)
+             for p in {leg.tune.get("prof", abi.SYN_FUZZ) for leg in args.legs}}
     out = {}
     for burst in args.sizes:
         res = alternate(args.legs, args.rounds, rng,
-                        lambda leg, rng: run_worker_leg(leg, args, burst, *pool),
+                        lambda leg, rng: run_worker_leg(
+                            leg, args, burst, *pools[leg.tune.get("prof", abi.SYN_FUZZ)]),
                         f"burst {burst}")
         out[str(burst)] = res
         report(res, args.legs[0].name, ("us_burst",), f"burst {burst:4d}",
@@ -340,8 +351,12 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.cmd == "dev" and [p for p in args.profiles if p not in PROFILES]:
         ap.error(f"--profiles: one of {', '.join(PROFILES)}")
-    if args.cmd == "worker" and [leg for leg in args.legs if leg.tune]:
-        ap.error("--legs: a worker leg takes no tuning")
+    if args.cmd == "worker" and [leg for leg in args.legs if set(leg.tune) - {"ext", "prof"}]:
+        ap.error("--legs: a worker leg takes no tuning (its own keys: ext=N, prof=N)")
+    if args.cmd == "worker" and [leg for leg in args.legs
+                                 if not 0 <= leg.tune.get("prof", 0) <= abi.SYN_FUZZ
+                                 or not 0 <= leg.tune.get("ext", 0) <= abi.EXT_ALL]:
+        ap.error("--legs: prof is an abi.SYN_* profile, ext a set of abi.EXT_* flags")
     try:
         args.run(args)
     except RuntimeError as err:   # a device fault or a failed submit: nothing more runs

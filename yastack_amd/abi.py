@@ -43,6 +43,8 @@ F_ASYNC = 0x2
 # extended mode (yrss_set_extended): this build's own semantics, not fs/lib's
 EXT_VLAN, EXT_IPV6, EXT_UDP = 0x1, 0x2, 0x4
 EXT_ALL = EXT_VLAN | EXT_IPV6 | EXT_UDP
+# yrss_worker_start_flags: route mode; the worker follows yrss_set_extended
+WORKER_F_ROUTE, WORKER_F_EXTENDED = 0x1, 0x2
 
 K_PARSE_HASH, K_SCAN, K_SCATTER = 0, 1, 2
 K_BURST, K_WORKER = 8, 9            # kernel ids of fault records only
@@ -225,6 +227,7 @@ _PROTOS = {
     "yrss_worker_submit_windows": (ctypes.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
                                                   ctypes.POINTER(ctypes.c_uint64)]),
     "yrss_worker_start_route": (ctypes.c_int, [_vp, _u32, _u32, ctypes.c_uint16]),
+    "yrss_worker_start_flags": (ctypes.c_int, [_vp, _u32, _u32, _u32, ctypes.c_uint16]),
     "yrss_worker_poll": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_int]),
     "yrss_worker_stop": (ctypes.c_int, [_vp]),
     "yrss_dispatch_frames_zc_ex": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
@@ -237,6 +240,7 @@ _PROTOS = {
                                         ctypes.POINTER(_vp)]),
     "yrss_fanout_fini": (ctypes.c_int, [_vp]),
     "yrss_fanout_size": (_u32, [_vp]),
+    "yrss_fanout_set_extended": (ctypes.c_int, [_vp, _u32]),
     "yrss_fanout_register_host_memory": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "yrss_fanout_unregister_host_memory": (ctypes.c_int, [_vp, _vp]),
     "yrss_fanout_submit": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32,
@@ -286,7 +290,8 @@ _PROTOS = {
 _SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists", "yrss_route_dev_seg",
               "yrss_route_seg", "yrss_worker_start_route", "yrss_route_lists_burst",
               "yrss_route_lists_frames", "yrss_route_lists",
-              "yrss_set_extended")   # (and the extended mode after them)
+              "yrss_set_extended",   # (and the extended mode after them,
+              "yrss_worker_start_flags", "yrss_fanout_set_extended")   # then its worker)
 
 # include/yrss_test_hooks.h (libyrss_test.so)
 _TEST_PROTOS = {

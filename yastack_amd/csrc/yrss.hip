@@ -3010,27 +3010,34 @@ struct WorkerParams {
 // cache: kWorkerOutCache slots x 4 addresses and one valid word per slot.
 // route: the KNI bitmaps sit in LDS too (16 KiB, built once per launch) and
 // nb is nq + 3; at the cap of 64 classes that is 148928 of the CU's 160 KiB.
-constexpr size_t worker_lds(uint32_t nb, bool route = false)
+// ext: the extended mode's nibble tables (4.5 KiB) lie before the control
+// words, where yrss_burst_small<..., true> has them: 153536 B at that cap.
+constexpr size_t worker_lds(uint32_t nb, bool route = false, bool ext = false)
 {
-    return small_lds(nb, route) + 64u + kWorkerOutCache * (32u + 4u);
+    return small_lds(nb, route, ext) + 64u + kWorkerOutCache * (32u + 4u);
 }
 static_assert(worker_lds(YRSS_ROUTE_LISTS_MAX_QUEUES + 3u, true) <= 160u * 1024u &&
+                  worker_lds(YRSS_ROUTE_LISTS_MAX_QUEUES + 3u, true, true) <= 160u * 1024u &&
                   YRSS_ROUTE_LISTS_MAX_QUEUES + 3u <= kSmallMaxNb,
-              "the route worker's LDS at the most classes fits one CU");
+              "the route worker's LDS at the most classes fits one CU, extended or not");
 
 // kRoute (yrss_worker_start_route): W.P.nb is nq + 3 and the lists the slot's
 // qidx / qstart addresses receive are the routed ones (nq + 4 offsets), under
 // W.P.route_lq / route_accept / kni_enable as the context held them at launch.
 // WorkerSlot has no room for a filter address: the class is computed, never
 // stored.
-template <bool kRoute>
+// kExt (yrss_worker_start_flags with YRSS_WORKER_F_EXTENDED, launched while the
+// context's flags are set): queue and hash by ext_classify under W.P.ext as
+// the context held it at launch (yrss_set_extended halts the worker); the
+// nibble tables are built once per launch, like the byte tables.
+template <bool kRoute, bool kExt = false>
 __global__ __launch_bounds__(kSmallBlock) void yrss_burst_worker(WorkerParams W)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t lane = lane_id();
     const SmallLds L = small_carve(smem, wave, W.P.nb);
-    uint32_t *ctl = reinterpret_cast<uint32_t *>(smem + small_lds(W.P.nb, kRoute));
+    uint32_t *ctl = reinterpret_cast<uint32_t *>(smem + small_lds(W.P.nb, kRoute, kExt));
     uint64_t *ocache = reinterpret_cast<uint64_t *>(ctl + 16);
     uint32_t *ovalid = reinterpret_cast<uint32_t *>(ocache + 4 * kWorkerOutCache);
     // slots of this workgroup: slot of ticket t is t mod nslots, and the
@@ -3039,6 +3046,9 @@ __global__ __launch_bounds__(kSmallBlock) void yrss_burst_worker(WorkerParams W)
     for (uint32_t i = threadIdx.x; i < kWorkerOutCache; i += blockDim.x)
         ovalid[i] = 0u;
     small_tables<kRoute>(W.P, L);
+    if (kExt)
+        build_ext_tables(L.kni + (kRoute ? kKniWords : 0), W.P.kni_bm + kKniWords, threadIdx.x,
+                         kSmallBlock);
 
     uint64_t t = __hip_atomic_load(W.next + blockIdx.x, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
@@ -3167,7 +3177,7 @@ __global__ __launch_bounds__(kSmallBlock) void yrss_burst_worker(WorkerParams W)
                            W.lens + (size_t)si * kWorkerMaxBurst, const_cast<uint8_t *>(P.win),
                            const_cast<uint16_t *>(P.len), W.fault + blockIdx.x, n, frames};
         if (n) {
-            small_burst_body<kRoute, 1, kRoute>(P, W.G, gio,
+            small_burst_body<kRoute, 1, kRoute, kExt>(P, W.G, gio,
                                     BurstIO{static_cast<uint32_t *>(out_ptr(2)),
                                             static_cast<uint32_t *>(out_ptr(3)),
                                             windows ? 0u : 1u,
@@ -3427,6 +3437,7 @@ struct yrss_ctx {
         bool on = false;           // yrss_worker_start called
         bool running = false;      // a worker launch may still be in flight
         bool route = false;        // yrss_worker_start_route: the lists are the routed ones
+        bool ext_ok = false;       // YRSS_WORKER_F_EXTENDED: follows yrss_set_extended
         uint16_t route_lq = 0;     // route: the lcore's own queue
         uint32_t nbk = 0;          // buckets of the lists: nb, or nb + 2 route classes
         uint32_t nslots = 0, nblocks = 0, qs_stride = 0;
@@ -4558,8 +4569,11 @@ int yrss_set_extended(yrss_ctx *c, uint32_t flags)
     if (c->pend.active)   // the burst in flight was queued under the old flags
         return -EBUSY;
     if (c->w.on) {
-        // a resident worker serves the reference's rules only: it is halted
-        // here and its submits are refused while flags are set
+        // the resident launch has the old flags (and the kernel that goes with
+        // them): it is halted here.  A worker started with
+        // YRSS_WORKER_F_EXTENDED is relaunched under the new flags by its next
+        // submit; any other serves the reference's rules only and refuses
+        // submits while flags are set
         if (c->w.pending)
             return -EBUSY;
         YRSS_HIP(hipSetDevice(c->device));
@@ -5444,12 +5458,26 @@ int worker_launch(yrss_ctx *c)
     W.idle_ticks = w.idle_ticks;
     W.life_ticks = w.life_ticks;
     W.poll_sleep = w.poll_sleep;
-    if (w.route)
-        hipLaunchKernelGGL(yrss_burst_worker<true>, dim3(w.nblocks), dim3(kSmallBlock),
-                           worker_lds(w.nbk, true), w.stream, W);
-    else
-        hipLaunchKernelGGL(yrss_burst_worker<false>, dim3(w.nblocks), dim3(kSmallBlock),
-                           worker_lds(c->nb), w.stream, W);
+    // flags set (an F_EXTENDED worker only: the others are refused before they
+    // get here): the kExt kernel and its LDS; flags 0: the plain kernel
+    const bool ext = c->ext != 0u;
+    if (ext && !w.ext_ok)
+        return -ENOTSUP;
+    if (w.route) {
+        if (ext)
+            hipLaunchKernelGGL((yrss_burst_worker<true, true>), dim3(w.nblocks),
+                               dim3(kSmallBlock), worker_lds(w.nbk, true, true), w.stream, W);
+        else
+            hipLaunchKernelGGL(yrss_burst_worker<true>, dim3(w.nblocks), dim3(kSmallBlock),
+                               worker_lds(w.nbk, true), w.stream, W);
+    } else {
+        if (ext)
+            hipLaunchKernelGGL((yrss_burst_worker<false, true>), dim3(w.nblocks),
+                               dim3(kSmallBlock), worker_lds(c->nb, false, true), w.stream, W);
+        else
+            hipLaunchKernelGGL(yrss_burst_worker<false>, dim3(w.nblocks), dim3(kSmallBlock),
+                               worker_lds(c->nb), w.stream, W);
+    }
     YRSS_HIP(hipGetLastError());
     w.running = true;
     return 0;
@@ -5470,20 +5498,24 @@ int worker_ensure(yrss_ctx *c)
     return rc ? rc : worker_launch(c);
 }
 
-int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uint16_t queue_id)
+int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uint16_t queue_id,
+                 bool extended)
 {
     if (!c || nblocks < 1 || nblocks > YRSS_WORKER_MAX_BLOCKS || nslots < nblocks ||
         nslots > YRSS_WORKER_MAX_SLOTS || nslots % nblocks || c->nb > kSmallMaxNb)
         return -EINVAL;
     if (route && c->cfg.nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
         return -ENOTSUP;
-    if (c->ext)   // the worker kernel has no extended variant (yrss_set_extended)
+    // a worker started without YRSS_WORKER_F_EXTENDED serves the reference's
+    // rules only, and says so by refusing (yrss_set_extended)
+    if (c->ext && !extended)
         return -ENOTSUP;
     if (c->w.on)
         return -EBUSY;
     YRSS_HIP(hipSetDevice(c->device));
     auto &w = c->w;
     w.route = route;
+    w.ext_ok = extended;
     w.route_lq = queue_id;
     w.nbk = route ? c->nb + 2u : c->nb;
     w.nslots = nslots;
@@ -5544,12 +5576,22 @@ extern "C" {
 
 int yrss_worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks)
 {
-    return worker_start(c, nslots, nblocks, false, 0);
+    return worker_start(c, nslots, nblocks, false, 0, false);
 }
 
 int yrss_worker_start_route(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, uint16_t queue_id)
 {
-    return worker_start(c, nslots, nblocks, true, queue_id);
+    return worker_start(c, nslots, nblocks, true, queue_id, false);
+}
+
+int yrss_worker_start_flags(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, uint32_t flags,
+                            uint16_t queue_id)
+{
+    if (!c || (flags & ~(uint32_t)(YRSS_WORKER_F_ROUTE | YRSS_WORKER_F_EXTENDED)))
+        return -EINVAL;
+    const bool route = (flags & YRSS_WORKER_F_ROUTE) != 0u;
+    return worker_start(c, nslots, nblocks, route, route ? queue_id : (uint16_t)0,
+                        (flags & YRSS_WORKER_F_EXTENDED) != 0u);
 }
 
 }  // extern "C"
@@ -5563,7 +5605,9 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     auto &w = c->w;
     if (!w.on)
         return -ENODEV;
-    if (c->ext)   // refused, not served by the reference's rules (yrss_set_extended)
+    // refused, not served by the reference's rules, unless the worker was
+    // started to follow the flags (yrss_worker_start_flags)
+    if (c->ext && !w.ext_ok)
         return -ENOTSUP;
     if (n > kWorkerMaxBurst)
         return -E2BIG;

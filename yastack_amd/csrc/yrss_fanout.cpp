@@ -23,6 +23,7 @@ struct yrss_fanout {
     std::vector<yrss_ctx *> ctx;
     uint64_t issued = 0;   // last ticket handed out (tickets start at 1)
     uint64_t handed = 0;   // last ticket returned by yrss_fanout_next
+    uint32_t ext = 0;      // YRSS_EXT_* every context holds (yrss_fanout_set_extended)
 };
 
 extern "C" {
@@ -66,7 +67,10 @@ int yrss_fanout_init(const struct yrss_config *cfg, const int *devices, uint32_t
         c.max_burst = 0;   // the worker has its own staging
         yrss_ctx *x = nullptr;
         int rc = yrss_init(&c, &x);
-        if (rc == 0 && (rc = yrss_worker_start(x, nslots, nblocks)) != 0)
+        // the workers follow yrss_fanout_set_extended; with flags 0 (as here)
+        // that is the plain worker's kernel
+        if (rc == 0 &&
+            (rc = yrss_worker_start_flags(x, nslots, nblocks, YRSS_WORKER_F_EXTENDED, 0)) != 0)
             yrss_fini(x);
         if (rc) {
             (void)yrss_fanout_fini(f);
@@ -75,6 +79,24 @@ int yrss_fanout_init(const struct yrss_config *cfg, const int *devices, uint32_t
         f->ctx.push_back(x);
     }
     *out = f;
+    return 0;
+}
+
+int yrss_fanout_set_extended(yrss_fanout *f, uint32_t flags)
+{
+    if (!f || (flags & ~(uint32_t)YRSS_EXT_ALL))
+        return -EINVAL;
+    if (f->handed != f->issued)   // a burst submitted under the old flags is outstanding
+        return -EBUSY;
+    for (size_t i = 0; i < f->ctx.size(); ++i) {
+        const int rc = yrss_set_extended(f->ctx[i], flags);
+        if (rc) {
+            while (i-- > 0)
+                (void)yrss_set_extended(f->ctx[i], f->ext);
+            return rc;
+        }
+    }
+    f->ext = flags;
     return 0;
 }
 

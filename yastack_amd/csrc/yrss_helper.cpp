@@ -94,8 +94,12 @@ int main(int argc, char **argv)
     int rc = yrss_init(&cfg, &ctx);
     if (rc == 0)
         rc = yrss_register_host_memory(ctx, map, bytes);
+    // the client's flags (yrss_remote_set_extended; 0: the reference's rules
+    // and the plain worker's kernel), fixed for this helper's lifetime
     if (rc == 0)
-        rc = yrss_worker_start(ctx, nslots, h->nblocks);
+        rc = yrss_set_extended(ctx, h->ext);
+    if (rc == 0)
+        rc = yrss_worker_start_flags(ctx, nslots, h->nblocks, YRSS_WORKER_F_EXTENDED, 0);
     if (rc != 0) {
         __atomic_store_n(&h->ready, rc < 0 ? rc : -EIO, __ATOMIC_RELEASE);
         if (ctx)

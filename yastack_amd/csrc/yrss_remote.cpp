@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "yrss_remote.h"
+#include "yrss_remote_ext.h"
 #include "yrss_remote_ring.h"
 
 extern char **environ;
@@ -297,6 +298,19 @@ int yrss_remote_restart(yrss_remote *r)
         kill_helper(r);
     }
     return spawn_helper(r);
+}
+
+int yrss_remote_set_extended(yrss_remote *r, uint32_t flags)
+{
+    if (!r || (flags & ~(uint32_t)YRSS_EXT_ALL))
+        return -EINVAL;
+    for (uint32_t si = 0; si < r->nslots; ++si)
+        if (!r->collected[si])
+            return -EBUSY;   // queued under the old flags: poll it first
+    // the helper reads the flags once, before it serves: a fresh one takes
+    // the new flags (and every later restart finds them here)
+    __atomic_store_n(&r->hdr->ext, flags, __ATOMIC_RELEASE);
+    return yrss_remote_restart(r);
 }
 
 pid_t yrss_remote_pid(const yrss_remote *r) { return r ? r->pid : -1; }

@@ -27,7 +27,7 @@
 namespace yrss_ring {
 
 constexpr uint32_t kMagic = 0x59525247u;   // "YRRG"
-constexpr uint32_t kVersion = 1;
+constexpr uint32_t kVersion = 2;            // 2: Header::ext
 constexpr uint32_t kWin = YRSS_WIN_FULL;   // window bytes per packet in a slot
 constexpr size_t kHeaderBytes = 4096;
 
@@ -39,7 +39,7 @@ struct alignas(64) Header {
     uint64_t map_bytes;
     uint64_t first;           // the helper's first ticket (restart resumes here)
     uint32_t inject;          // fault injection for tests: 1 = never complete a burst
-    uint32_t pad0;
+    uint32_t ext;             // YRSS_EXT_* the helper sets on its context before it serves
     struct yrss_config cfg;
     alignas(64) uint32_t stop;        // client: leave
     alignas(64) int32_t ready;        // helper: 0 starting, 1 serving, < 0 -errno

@@ -259,8 +259,9 @@ class SoftRss:
         (``yrss_set_extended``): ``vlan`` classifies a frame as if its one or
         two VLAN tags had been stripped, ``ipv6`` hashes IPv6 TCP over the 36
         wire-order tuple bytes, ``udp`` lets UDP take the TCP branch.  All
-        False restores the reference's rules exactly.  The persistent worker
-        refuses bursts (ENOTSUP) while any flag is set."""
+        False restores the reference's rules exactly.  A persistent worker
+        started with ``extended=True`` follows the flags; any other refuses
+        bursts (ENOTSUP) while a flag is set."""
         flags = (abi.EXT_VLAN if vlan else 0) | (abi.EXT_IPV6 if ipv6 else 0) | \
             (abi.EXT_UDP if udp else 0)
         abi.check(self._lib.yrss_set_extended(self._ctx, flags), "yrss_set_extended")
@@ -398,14 +399,22 @@ class SoftRss:
 
     # -- persistent burst worker ------------------------------------------------
     def worker_start(self, nslots: int = 16, nblocks: int = 4,
-                     route_queue_id: int | None = None) -> None:
+                     route_queue_id: int | None = None, extended: bool = False) -> None:
         """Start the persistent small-burst worker (``yrss_worker_start``).
         With ``route_queue_id`` (``yrss_worker_start_route``, nb_queues <= 61)
         every burst's ``qidx`` / ``qstart`` are the routed lists for the lcore
         whose queue that is: packet indices grouped by route class
         (``segments.route_buckets``) and nb_queues + 4 offsets, under the KNI
-        state of the last :meth:`set_kni`; :meth:`route_lists` hands them off."""
-        if route_queue_id is None:
+        state of the last :meth:`set_kni`; :meth:`route_lists` hands them off.
+        ``extended`` (``yrss_worker_start_flags``, ``WORKER_F_EXTENDED``): the
+        worker follows :meth:`set_extended` instead of refusing bursts while
+        a flag is set."""
+        if extended:
+            flags = abi.WORKER_F_EXTENDED | (0 if route_queue_id is None else abi.WORKER_F_ROUTE)
+            abi.check(self._lib.yrss_worker_start_flags(self._ctx, nslots, nblocks, flags,
+                                                        route_queue_id or 0),
+                      "yrss_worker_start_flags")
+        elif route_queue_id is None:
             abi.check(self._lib.yrss_worker_start(self._ctx, nslots, nblocks),
                       "yrss_worker_start")
         else:
@@ -732,6 +741,14 @@ class FanOut:
     def unregister_host_memory(self, base: int) -> None:
         abi.check(self._lib.yrss_fanout_unregister_host_memory(self._f, base),
                   "yrss_fanout_unregister_host_memory")
+
+    def set_extended(self, vlan: bool = False, ipv6: bool = False, udp: bool = False) -> None:
+        """:meth:`SoftRss.set_extended` on every context
+        (``yrss_fanout_set_extended``); EBUSY while a ticket is outstanding."""
+        flags = (abi.EXT_VLAN if vlan else 0) | (abi.EXT_IPV6 if ipv6 else 0) | \
+            (abi.EXT_UDP if udp else 0)
+        abi.check(self._lib.yrss_fanout_set_extended(self._f, flags), "yrss_fanout_set_extended")
+        self.ext_flags = flags
 
     def _queue(self, name, n, call) -> int:
         """As SoftRss._worker_queue: ``call(outs, ticket)`` makes the C call ``name``."""

@@ -30,6 +30,7 @@ _PROTOS = {
     "yrss_remote_submit": (ctypes.c_int, [_vp, _vp, _vp, _u32, ctypes.POINTER(ctypes.c_uint64)]),
     "yrss_remote_poll": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "yrss_remote_restart": (ctypes.c_int, [_vp]),
+    "yrss_remote_set_extended": (ctypes.c_int, [_vp, _u32]),
     "yrss_remote_pid": (ctypes.c_int, [_vp]),
     "yrss_remote_stop": (ctypes.c_int, [_vp]),
 }
@@ -97,6 +98,16 @@ class RemoteRss:
 
     def restart(self) -> None:
         abi.check(self._lib.yrss_remote_restart(self._r), "yrss_remote_restart")
+
+    def set_extended(self, vlan: bool = False, ipv6: bool = False, udp: bool = False) -> None:
+        """The extended mode for the helper's context
+        (``yrss_remote_set_extended``): a fresh helper replaces this one and
+        serves under the flags, which later restarts keep.  EBUSY while a
+        submitted ticket has not been polled."""
+        flags = (abi.EXT_VLAN if vlan else 0) | (abi.EXT_IPV6 if ipv6 else 0) | \
+            (abi.EXT_UDP if udp else 0)
+        abi.check(self._lib.yrss_remote_set_extended(self._r, flags), "yrss_remote_set_extended")
+        self.ext_flags = flags
 
     def stop(self) -> int:
         rc = 0

@@ -249,6 +249,67 @@ int yrss_set_kni(yrss_ctx *ctx, int enable, const char *method,
 #define YRSS_EXT_ALL  0x7u
 int yrss_set_extended(yrss_ctx *ctx, uint32_t flags);
 
+/* ---- redirection table: THIS BUILD'S OWN SEMANTICS, NOT fs/lib's -------------- */
+
+/* toeplitz_dispatch picks a hashed packet's queue as hash % d (+1), d fixed by
+ * nb_procs and dispatch_only_core (ff_dpdk_if.c:2031-2034).  That is the
+ * default here too, bit for bit.  An RSS redirection table (RETA) is an opt-in
+ * departure, per context, for deployments that want to weight, drain or
+ * rebalance their lcores without renumbering every flow; nothing in fs/lib
+ * computes these results.
+ *
+ * While a table is set, a hashed packet's queue is table[hash & (size - 1)].
+ * "Hashed" means hashed under the rules in force: the reference's with
+ * yrss_set_extended flags 0, the extended mode's otherwise.  Nothing else
+ * moves: the hash output is the same; an unhashed packet keeps its constant
+ * queue (0 for ARP / RARP, YRSS_DEFAULT_Q); a hashed packet whose ports lie
+ * beyond the window stays YRSS_Q_TRUNCATED with hash 0; the protocol_filter
+ * class still follows the reference on the unstripped frame.  Per-queue lists,
+ * segmented lists and route classes follow the new queue.  dispatch_only_core
+ * does not constrain the table: an entry may name queue 0, the table being the
+ * operator's statement.
+ *
+ * yrss_set_reta: size is a power of two, 1..YRSS_RETA_MAX, and every entry is
+ * < nb_queues of the context; anything else is -EINVAL and the table in force
+ * stays as it was.  table == NULL or size == 0 switches the table off and
+ * restores hash % d (+1) exactly.  -EBUSY while a YRSS_F_ASYNC or worker burst
+ * is pending.  The table is copied (the caller's array is free on return) and
+ * holds for every dispatch issued after the call returns, so an lcore rewrites
+ * it between two bursts; a device batch still running on a caller's stream may
+ * see either table.
+ * yrss_get_reta copies the table in force into table[cap] and returns its
+ * size, 0 when none is set; -EINVAL when cap is smaller than that size.
+ *
+ * Honoured by every yrss_dispatch_dev*, yrss_route_dev_seg, the host bursts
+ * and frames (zero-copy and routed forms included), yrss_route_burst and by
+ * yrss_toeplitz_dispatch on a context without a worker.
+ * NOT served yet: the persistent worker, and so the helper process
+ * (yrss_remote_*) and the fan-out (yrss_fanout_*), which are built on it and
+ * have no table call.  While a table is set yrss_worker_start* and every
+ * yrss_worker_submit* return -ENOTSUP, YRSS_WORKER_F_EXTENDED workers
+ * included, and the shim on a worker context returns -1; a resident worker is
+ * halted by yrss_set_reta as yrss_set_extended halts it, and serves again
+ * from the first submit after the table is cleared.  yrss_rss_check_dev and
+ * yrss_rss_lport_sweep are unchanged: they model the NIC's RSS over the raw
+ * network-order tuple, not this dispatcher's hash, and take their own
+ * reta_size.
+ *
+ * yrss_reta_fill_weighted is pure host code and needs no context: it fills
+ * table[size] (a power of two, 1..YRSS_RETA_MAX) with the queue ids
+ * 0..nb_queues - 1 in proportion to weights[nb_queues] by smooth weighted
+ * round-robin.  Every queue has a running value, 0 at the start; for each
+ * slot in order: add each queue's weight to its value, take the queue with
+ * the largest value (the lowest index on ties), subtract the sum of all
+ * weights from that queue's value, write that queue's id to the slot.  A
+ * queue's count is within 1 of size * w / W; weight 0 means the queue never
+ * appears; equal weights give table[i] == i % nb_queues.  -EINVAL when every
+ * weight is 0, nb_queues is 0 or above YRSS_MAX_QUEUES, or the size is bad. */
+#define YRSS_RETA_MAX 512
+int yrss_set_reta(yrss_ctx *ctx, const uint16_t *table, uint32_t size);
+int yrss_get_reta(yrss_ctx *ctx, uint16_t *table, uint32_t cap);   /* returns size, 0 when off */
+int yrss_reta_fill_weighted(uint16_t *table, uint32_t size,
+                            const uint32_t *weights, uint32_t nb_queues);
+
 /* Full device batch: yrss_dispatch_dev plus the optional filter output. */
 struct yrss_dev_batch {
     const uint8_t *win;       /* as d_win of yrss_dispatch_dev          */

@@ -15,7 +15,9 @@ own max - min over its repeats.  The base is the first leg given.
 A leg is [name=]lib[@k=v;k=v][:form].  lib: cur, test (libyrss_test.so) or a
 path, relative to the repository root or absolute (tools/build_ab_lib.sh).
 k=v: yrss_set_tuning fields, side=1 (the batches on a non-default stream),
-ext=N (yrss_set_extended flags: 1 VLAN, 2 IPv6, 4 UDP), dbg_groups / dbg_merge (the test library's hooks); dev legs only.  form, dev:
+ext=N (yrss_set_extended flags: 1 VLAN, 2 IPv6, 4 UDP), reta=SIZE (yrss_set_reta: an
+equal-weights table of SIZE entries over the context's queues), dbg_groups /
+dbg_merge (the test library's hooks); dev legs only.  form, dev:
 global (default), seg, seg-filter, route; worker: plain (default), route.
 A worker leg takes two keys of its own: ext=N starts the worker with
 YRSS_WORKER_F_EXTENDED under flags N (ext=0: that worker with the flags off;
@@ -53,6 +55,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 from yastack_amd import SoftRss, abi  # noqa: E402
+from yastack_amd.dispatch import reta_weighted  # noqa: E402
 
 Leg = namedtuple("Leg", "name lib tune form")
 
@@ -171,6 +174,9 @@ def run_dev_leg(leg, rng, args, npr, profile):
     ext = tn.pop("ext", 0)
     if ext:
         e.set_extended(vlan=bool(ext & 1), ipv6=bool(ext & 2), udp=bool(ext & 4))
+    reta = tn.pop("reta", 0)
+    if reta:
+        e.set_reta(reta_weighted([1] * npr, reta))
     if tn.pop("dbg_merge", 0):
         assert e._lib.yrss_debug_partial_merge(e._ctx, 1) == 0
     if grp:

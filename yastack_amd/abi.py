@@ -43,6 +43,8 @@ F_ASYNC = 0x2
 # extended mode (yrss_set_extended): this build's own semantics, not fs/lib's
 EXT_VLAN, EXT_IPV6, EXT_UDP = 0x1, 0x2, 0x4
 EXT_ALL = EXT_VLAN | EXT_IPV6 | EXT_UDP
+# redirection table (yrss_set_reta): entries at the most; the build's own semantics too
+RETA_MAX = 512
 # yrss_worker_start_flags: route mode; the worker follows yrss_set_extended
 WORKER_F_ROUTE, WORKER_F_EXTENDED = 0x1, 0x2
 
@@ -256,6 +258,9 @@ _PROTOS = {
     "yrss_set_kni": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p,
                                     ctypes.c_char_p]),
     "yrss_set_extended": (ctypes.c_int, [_vp, _u32]),
+    "yrss_set_reta": (ctypes.c_int, [_vp, _vp, _u32]),
+    "yrss_get_reta": (ctypes.c_int, [_vp, _vp, _u32]),
+    "yrss_reta_fill_weighted": (ctypes.c_int, [_vp, _u32, _vp, _u32]),
     "yrss_dispatch_dev_ex": (ctypes.c_int, [_vp, ctypes.POINTER(DevBatch), _vp]),
     "yrss_dispatch_dev_seg": (ctypes.c_int, [_vp, ctypes.POINTER(DevSegBatch), _vp]),
     "yrss_seg_to_lists": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
@@ -291,7 +296,8 @@ _SINCE_SEG = ("yrss_dispatch_dev_seg", "yrss_seg_to_lists", "yrss_route_dev_seg"
               "yrss_route_seg", "yrss_worker_start_route", "yrss_route_lists_burst",
               "yrss_route_lists_frames", "yrss_route_lists",
               "yrss_set_extended",   # (and the extended mode after them,
-              "yrss_worker_start_flags", "yrss_fanout_set_extended")   # then its worker)
+              "yrss_worker_start_flags", "yrss_fanout_set_extended",   # then its worker,
+              "yrss_set_reta", "yrss_get_reta", "yrss_reta_fill_weighted")   # then the table)
 
 # include/yrss_test_hooks.h (libyrss_test.so)
 _TEST_PROTOS = {

@@ -88,6 +88,11 @@ constexpr int kExtTupleBytes = 36;
 constexpr int kExtWins = 8 * kExtTupleBytes;          // 288
 constexpr int kExtTblWords = 2 * kExtTupleBytes * 16; // 1152
 constexpr int kExtTblBytes = kExtTblWords * 4;
+// Redirection table (yrss_set_reta; the build's own semantics as well): always
+// YRSS_RETA_MAX uint16 entries, 1 KiB, behind the extended key windows in the
+// context's KNI buffer and behind the nibble tables in a kReta kernel's LDS.
+constexpr int kRetaWords = YRSS_RETA_MAX / 2;         // 256
+constexpr int kRetaBytes = kRetaWords * 4;
 
 // Everything yrss_parse_hash needs, passed by value (kernarg segment).
 struct ParseParams {
@@ -107,6 +112,9 @@ struct ParseParams {
     uint32_t nq;          // nb_queues
     uint32_t nb;          // buckets = nq + 1 (last = drop)
     uint32_t mod_d;       // divisor: nb_procs or nb_procs-1
+                          // (a kReta launch reads no divisor: the word carries the
+                          // redirection table's size there, a power of two <=
+                          // YRSS_RETA_MAX, and q_off and mod_m go unread)
     uint32_t q_off;       // 0 or 1 (dispatch_only_core)
     uint64_t mod_m;       // Lemire fastmod constant for mod_d
     int8_t *filter;       // protocol_filter class per packet, or null
@@ -126,7 +134,8 @@ struct ParseParams {
     uint32_t kwin[96];    // key window at every tuple bit position
     uint32_t ext;         // kExt kernels: YRSS_EXT_* (yrss_set_extended); their 288 key
                           // windows follow the KNI bitmaps at kni_bm + kKniWords
-                          // (the word sits in what was padding, like route_lq)
+                          // (the word sits in what was padding, like route_lq);
+                          // kReta kernels: the redirection table follows the windows
     uint8_t *seg_idx;     // kCount == 3: per 256-packet segment, its packets' segment-local
                           // indices grouped by bucket (yrss_dispatch_dev_seg)
     uint16_t *seg_off;    // kCount == 3: [segments][nb + 1] bucket offsets inside a segment
@@ -522,6 +531,15 @@ __device__ __forceinline__ void build_ext_tables(uint32_t *xtbl, const uint32_t 
     }
 }
 
+// The redirection table (yrss_set_reta): its YRSS_RETA_MAX uint16 entries, two
+// a word, from device memory (entries past the size in force are zero).
+__device__ __forceinline__ void load_reta(uint32_t *rtbl, const uint32_t *src, uint32_t tid,
+                                          uint32_t nthr)
+{
+    for (uint32_t e = tid; e < (uint32_t)kRetaWords; e += nthr)
+        rtbl[e] = src[e];
+}
+
 // Toeplitz over tuple word k (wire order, first byte on top): eight lookups
 // into nibble tables 8k .. 8k + 7.
 __device__ __forceinline__ uint32_t tz_nib(uint32_t w, const uint32_t *xt)
@@ -546,11 +564,15 @@ __device__ __forceinline__ uint32_t tz_nib(uint32_t w, const uint32_t *xt)
 // is the same bytes of a dword t further on.  Dwords past the staged 64 bytes
 // come from HBM while they lie inside the window (4 i + 4 <= stride, and the
 // stride is a multiple of 16); ports that end beyond it give YRSS_Q_TRUNCATED.
+// kReta (yrss_set_reta): a hashed packet's queue is rtbl[h & (size - 1)], one
+// LDS read at a per-lane index, in place of h % d + q_off; the table sits
+// behind the nibble tables and P.mod_d carries its size.  Nothing else moves.
 struct ExtResult {
     int q;
     uint32_t h;
 };
 
+template <bool kReta = false>
 __device__ __forceinline__ ExtResult ext_classify(const ParseParams &P, const uint32_t *tbl,
                                                   const uint32_t *xtbl, const uint32_t *mine,
                                                   uint32_t rsw, uint32_t pkt, bool valid,
@@ -632,10 +654,16 @@ __device__ __forceinline__ ExtResult ext_classify(const ParseParams &P, const ui
         }
     }
     if (hashed) {
-        const uint32_t rem = (P.mod_d & (P.mod_d - 1u)) == 0u
-                                 ? h & (P.mod_d - 1u)
-                                 : (uint32_t)__umul64hi(P.mod_m * (uint64_t)h, (uint64_t)P.mod_d);
-        qv = (int)(uint16_t)(rem + P.q_off);
+        if (kReta) {
+            const uint16_t *rtbl = reinterpret_cast<const uint16_t *>(xtbl + kExtTblWords);
+            qv = (int)rtbl[h & (P.mod_d - 1u)];
+        } else {
+            const uint32_t rem =
+                (P.mod_d & (P.mod_d - 1u)) == 0u
+                    ? h & (P.mod_d - 1u)
+                    : (uint32_t)__umul64hi(P.mod_m * (uint64_t)h, (uint64_t)P.mod_d);
+            qv = (int)(uint16_t)(rem + P.q_off);
+        }
         if (trunc) {
             qv = YRSS_Q_TRUNCATED;
             h = 0u;
@@ -646,7 +674,8 @@ __device__ __forceinline__ ExtResult ext_classify(const ParseParams &P, const ui
 
 // kExt: queue and hash by ext_classify (xtbl: its nibble tables); the
 // protocol_filter class still follows the reference on the unstripped frame.
-template <int kCount, bool kFilter, bool kExt = false>
+// kReta (with kExt only): ext_classify's queue comes from the redirection table.
+template <int kCount, bool kFilter, bool kExt = false, bool kReta = false>
 __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_t *tbl,
                                              const uint32_t *kni, u32x4 *stage, uint32_t *cnt,
                                              const OutSlot &ob, uint32_t t0, uint32_t end,
@@ -700,7 +729,7 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
     const bool hashed = !kExt && ip_ok && (L - ihl4) >= 20u && proto == 6u;
     uint32_t h = 0;
     if (kExt) {
-        const ExtResult x = ext_classify(P, tbl, xtbl, mine, rsw, pkt, valid, L);
+        const ExtResult x = ext_classify<kReta>(P, tbl, xtbl, mine, rsw, pkt, valid, L);
         qv = x.q;
         h = x.h;
     }
@@ -822,14 +851,17 @@ __device__ __forceinline__ void process_tile(const ParseParams &P, const uint32_
 //   kBlock   workgroup size (256/512): waves per CU, one key table per group
 //   kExt     extended mode (ext_classify): 4.5 KiB of nibble tables after the
 //            KNI bitmaps; the other variants are the code they were without it
+//   kReta    redirection table (yrss_set_reta; with kExt only): 1 KiB behind
+//            the nibble tables, copied from behind the extended key windows
 // Window loads are non-temporal (streaming): ~25 % faster than default-policy
 // loads (profiles/r01_v32_nt_ab.log).
 // LDS: key tables 12 KiB | staging 4 KiB per wave | count slots 8 KiB per wave |
 //      output buffer 2.25 KiB per wave | KNI bitmaps 16 KiB (kFilter only).
 // ---------------------------------------------------------------------------
-template <int kCount, bool kFilter, int kBlock, bool kExt = false>
+template <int kCount, bool kFilter, int kBlock, bool kExt = false, bool kReta = false>
 __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
 {
+    static_assert(kExt || !kReta, "the table rule lives in ext_classify");
     constexpr int kWaves = kBlock / kWave;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t *tbl = reinterpret_cast<uint32_t *>(smem);
@@ -854,6 +886,8 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
     build_key_tables(tbl, P.kwin, threadIdx.x, kBlock);
     if (kExt)
         build_ext_tables(xtbl, P.kni_bm + kKniWords, threadIdx.x, kBlock);
+    if (kReta)
+        load_reta(xtbl + kExtTblWords, P.kni_bm + kKniWords + kExtWins, threadIdx.x, kBlock);
     if (kFilter)
         for (uint32_t e = threadIdx.x; e < (uint32_t)kKniWords; e += kBlock)
             kni[e] = P.kni_enable ? P.kni_bm[e] : 0u;
@@ -928,15 +962,15 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
         for (uint32_t i = 0;; i += 2) {
             const bool hB = tile_at(i + 1, tB, sB);
             load_tile<true>(P, hB ? tB : tA, P.n, lane, rB, LB);
-            process_tile<kC, kFilter, kExt>(P, tbl, kni, stage, cnt_w + sA * P.nb, slot(i), tA,
-                                            P.n, lane, rA, LA, xtbl);
+            process_tile<kC, kFilter, kExt, kReta>(P, tbl, kni, stage, cnt_w + sA * P.nb,
+                                                   slot(i), tA, P.n, lane, rA, LA, xtbl);
             after(i, tA, !hB);
             if (!hB)
                 break;
             const bool hA = tile_at(i + 2, tA, sA);
             load_tile<true>(P, hA ? tA : tB, P.n, lane, rA, LA);
-            process_tile<kC, kFilter, kExt>(P, tbl, kni, stage, cnt_w + sB * P.nb, slot(i + 1),
-                                            tB, P.n, lane, rB, LB, xtbl);
+            process_tile<kC, kFilter, kExt, kReta>(P, tbl, kni, stage, cnt_w + sB * P.nb,
+                                                   slot(i + 1), tB, P.n, lane, rB, LB, xtbl);
             after(i + 1, tB, !hA);
             if (!hA)
                 break;
@@ -2730,14 +2764,18 @@ struct SmallParams {
     uint64_t seq;        // stored into *done once every output is visible to the host
 };
 
-__host__ __device__ constexpr size_t small_lds(uint32_t nb, bool filter, bool ext = false)
+__host__ __device__ constexpr size_t small_lds(uint32_t nb, bool filter, bool ext = false,
+                                               bool reta = false)
 {
     return kTblBytes + kSmallWaves * (kStageBytes + kOutBytes) +
            (size_t)(kSmallTiles * nb + kSmallMaxNb) * sizeof(uint32_t) +
-           (filter ? kKniWords * sizeof(uint32_t) : 0u) + (ext ? kExtTblBytes : 0u);
+           (filter ? kKniWords * sizeof(uint32_t) : 0u) + (ext ? kExtTblBytes : 0u) +
+           (reta ? kRetaBytes : 0u);
 }
 static_assert(small_lds(kSmallMaxNb, true, true) <= 160u * 1024u,
               "the extended one-launch kernel's LDS at the most buckets fits one CU");
+static_assert(small_lds(kSmallMaxNb, true, true, true) <= 160u * 1024u,
+              "and with the redirection table behind it (148.75 + 1 KiB)");
 
 // LDS carve-up shared by the one-shot kernel and the worker.
 struct SmallLds {
@@ -2798,7 +2836,7 @@ struct BurstIO {
 // global (one start row, 32-bit indices): no segment, so the only limit is one
 // lane per class, nq + 3 <= 64.
 template <bool kFilter, uint32_t kTW = kOutTiles,   // kTW: tiles per wave (n <= kTW * 1024)
-          bool kRoute = false, bool kExt = false>
+          bool kRoute = false, bool kExt = false, bool kReta = false>
 __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, const GatherIO &gio,
                                  const BurstIO &S, const SmallLds &L, uint32_t wave,
                                  uint32_t lane)
@@ -2830,7 +2868,7 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
             break;
         static_assert(!kRoute || kFilter, "route classes need the filter class");
         // (kCount 4 is kCount 2 without the rank tag, over route_bucket)
-        process_tile<kRoute ? 4 : 2, kFilter, kExt>(
+        process_tile<kRoute ? 4 : 2, kFilter, kExt, kReta>(
             P, L.tbl, L.kni, L.stage, L.cnt + t * P.nb,
             OutSlot{L.oq + j * kTile, L.oh + j * kTile, L.of + j * kTile, L.orank + j * kTile},
             t * kTile, P.n, lane, r[j], Ln[j], L.kni + (kFilter ? kKniWords : 0));
@@ -2892,10 +2930,12 @@ __device__ void small_burst_body(const ParseParams &P, const GatherParams &G, co
 }
 
 // kExt: extended mode (ext_classify), its nibble tables after the KNI bitmaps
-// (after the start row without them).
-template <bool kFilter, bool kRoute = false, bool kExt = false>
+// (after the start row without them).  kReta (with kExt only): the redirection
+// table behind them.
+template <bool kFilter, bool kRoute = false, bool kExt = false, bool kReta = false>
 __global__ __launch_bounds__(kSmallBlock) void yrss_burst_small(SmallParams S)
 {
+    static_assert(kExt || !kReta, "the table rule lives in ext_classify");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const SmallLds L = small_carve(smem, wave, S.P.nb);
@@ -2903,7 +2943,10 @@ __global__ __launch_bounds__(kSmallBlock) void yrss_burst_small(SmallParams S)
     if (kExt)
         build_ext_tables(L.kni + (kFilter ? kKniWords : 0), S.P.kni_bm + kKniWords, threadIdx.x,
                          kSmallBlock);
-    small_burst_body<kFilter, kOutTiles, kRoute, kExt>(
+    if (kReta)
+        load_reta(L.kni + (kFilter ? kKniWords : 0) + kExtTblWords,
+                  S.P.kni_bm + kKniWords + kExtWins, threadIdx.x, kSmallBlock);
+    small_burst_body<kFilter, kOutTiles, kRoute, kExt, kReta>(
         S.P, S.G, gather_io(S.G), BurstIO{S.qidx, S.qstart, S.gather, S.writeback}, L, wave,
         lane_id());
     if (S.done) {
@@ -3386,6 +3429,8 @@ struct yrss_ctx {
     bool kni_accept = false;
     uint8_t kni_bm[2 * 8192] = {};   // tcp bitmap then udp bitmap, htons-indexed
     uint32_t ext = 0;                // YRSS_EXT_* (yrss_set_extended); 0: the reference's rules
+    uint32_t reta_size = 0;          // yrss_set_reta: entries in force; 0: hash % d (+1)
+    uint16_t reta[YRSS_RETA_MAX] = {};   // (zero past reta_size, as on the device)
     struct Occ {
         const void *fn;
         uint32_t block, lds, blocks;
@@ -3411,7 +3456,8 @@ struct yrss_ctx {
     // what lives as long as the context
     BufOwner own;
     PinnedBuf<uint32_t> fault_rec;  // host-coherent fault record {code, kernel, where, value}
-    DevBuf<uint32_t> kni;           // the KNI bitmaps, then the 288 extended key windows
+    DevBuf<uint32_t> kni;           // the KNI bitmaps, the 288 extended key windows, then
+                                    // the redirection table (kRetaWords)
     Staged<uint32_t> fault;         // zero-copy gather fault word (h host-coherent)
     PinnedBuf<uint64_t> done;       // host-coherent completion word of yrss_burst_small
     uint64_t done_seq = 0;
@@ -3505,14 +3551,18 @@ namespace {
 
 constexpr uint32_t kParseBlock = 512;   // 8 waves: one workgroup per CU (LDS)
 
-constexpr size_t parse_lds(bool filter, bool ext = false)
+constexpr size_t parse_lds(bool filter, bool ext = false, bool reta = false)
 {
     constexpr size_t w = kParseBlock / kWave;
     return kTblBytes + w * kStageBytes + w * (kCntWords * sizeof(uint32_t) + kOutBytes) +
-           (filter ? kKniWords * sizeof(uint32_t) : 0u) + (ext ? kExtTblBytes : 0u);
+           (filter ? kKniWords * sizeof(uint32_t) : 0u) + (ext ? kExtTblBytes : 0u) +
+           (reta ? kRetaBytes : 0u);
 }
 static_assert(parse_lds(true, true) <= 160u * 1024u,
               "the extended filter variant's LDS (150.5 KiB) fits one CU");
+static_assert(parse_lds(true, true, true) == 151u * 1024u + 512u &&
+                  parse_lds(true, true, true) <= 160u * 1024u,
+              "and with the redirection table behind it (150.5 + 1 KiB)");
 
 // One workgroup per CU (the LDS of the filter variant admits no second), so
 // the grid does not depend on whether the filter is on and a batch's layout
@@ -3662,25 +3712,29 @@ typedef void (*ParseKernel)(ParseParams);
 // 3 segmented lists (yrss_dispatch_dev_seg only), 4 segmented lists over route
 // classes (yrss_route_dev_seg only; always with the filter class)
 // ext: the extended-mode instantiations (yrss_set_extended)
-template <bool kExt>
+// reta: the redirection-table instantiations (yrss_set_reta): kExt kernels
+// whatever the flags (with P.ext == 0 ext_classify is the reference's rule)
+template <bool kExt, bool kReta = false>
 ParseKernel pick_parse_of(int count, bool filter)
 {
     if (count == 4)
-        return yrss_parse_hash<4, true, kParseBlock, kExt>;
+        return yrss_parse_hash<4, true, kParseBlock, kExt, kReta>;
     if (count == 3)
-        return filter ? yrss_parse_hash<3, true, kParseBlock, kExt>
-                      : yrss_parse_hash<3, false, kParseBlock, kExt>;
+        return filter ? yrss_parse_hash<3, true, kParseBlock, kExt, kReta>
+                      : yrss_parse_hash<3, false, kParseBlock, kExt, kReta>;
     if (filter)
-        return count == 2 ? yrss_parse_hash<2, true, kParseBlock, kExt>
-               : count    ? yrss_parse_hash<1, true, kParseBlock, kExt>
-                          : yrss_parse_hash<0, true, kParseBlock, kExt>;
-    return count == 2 ? yrss_parse_hash<2, false, kParseBlock, kExt>
-           : count    ? yrss_parse_hash<1, false, kParseBlock, kExt>
-                      : yrss_parse_hash<0, false, kParseBlock, kExt>;
+        return count == 2 ? yrss_parse_hash<2, true, kParseBlock, kExt, kReta>
+               : count    ? yrss_parse_hash<1, true, kParseBlock, kExt, kReta>
+                          : yrss_parse_hash<0, true, kParseBlock, kExt, kReta>;
+    return count == 2 ? yrss_parse_hash<2, false, kParseBlock, kExt, kReta>
+           : count    ? yrss_parse_hash<1, false, kParseBlock, kExt, kReta>
+                      : yrss_parse_hash<0, false, kParseBlock, kExt, kReta>;
 }
 
-ParseKernel pick_parse(int count, bool filter, bool ext)
+ParseKernel pick_parse(int count, bool filter, bool ext, bool reta)
 {
+    if (reta)
+        return pick_parse_of<true, true>(count, filter);
     if (ext)
         return pick_parse_of<true>(count, filter);
     if (count == 4)
@@ -3714,6 +3768,8 @@ ParseParams parse_params(const yrss_ctx *c, int route_lq, bool out16)
     P.kni_bm = c->kni.d;
     P.kni_enable = c->kni_enable ? 1u : 0u;
     P.ext = c->ext;
+    if (c->reta_size)   // kReta launches (pick_parse): the size where the divisor was
+        P.mod_d = c->reta_size;
     P.out16 = out16 ? 1u : 0u;
     if (route_lq >= 0) {
         P.nb = c->nb + 2u;
@@ -4025,9 +4081,20 @@ int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = tru
     } else {
         S.done = nullptr;
     }
-    const size_t lds = small_lds(S.P.nb, filter || route, S.P.ext != 0u);
+    const bool reta = c->reta_size != 0u;   // (S.P.mod_d is then the table's size)
+    const size_t lds = small_lds(S.P.nb, filter || route, reta || S.P.ext != 0u, reta);
     const dim3 grid(1);
-    if (S.P.ext) {
+    if (reta) {
+        if (route)
+            hipLaunchKernelGGL((yrss_burst_small<true, true, true, true>), grid,
+                               dim3(kSmallBlock), lds, stream, S);
+        else if (filter)
+            hipLaunchKernelGGL((yrss_burst_small<true, false, true, true>), grid,
+                               dim3(kSmallBlock), lds, stream, S);
+        else
+            hipLaunchKernelGGL((yrss_burst_small<false, false, true, true>), grid,
+                               dim3(kSmallBlock), lds, stream, S);
+    } else if (S.P.ext) {
         if (route)
             hipLaunchKernelGGL((yrss_burst_small<true, true, true>), grid, dim3(kSmallBlock), lds,
                                stream, S);
@@ -4436,13 +4503,14 @@ int yrss_init(const struct yrss_config *cfg, yrss_ctx **out)
     hipError_t e;
     if ((e = list_ws_alloc(c, c->ws)) != hipSuccess ||
         (e = c->fault_rec.alloc(c->own, 16, hipHostMallocCoherent)) != hipSuccess ||   // 64 B
-        (e = c->kni.alloc(c->own, kKniWords + kExtWins)) != hipSuccess ||
+        (e = c->kni.alloc(c->own, kKniWords + kExtWins + kRetaWords)) != hipSuccess ||
         (e = c->fault.alloc(c->own, 1)) != hipSuccess ||
         (e = c->fault.alloc(c->own, 1, hipHostMallocCoherent)) != hipSuccess ||
         (e = c->done.alloc(c->own, 8, hipHostMallocCoherent)) != hipSuccess ||        // 64 B
         (e = hipMemset(c->kni.d, 0, sizeof(c->kni_bm))) != hipSuccess ||
         (e = hipMemcpy(c->kni.d + kKniWords, xwin, sizeof(xwin), hipMemcpyHostToDevice)) !=
             hipSuccess ||
+        (e = hipMemset(c->kni.d + kKniWords + kExtWins, 0, kRetaBytes)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming)) != hipSuccess) {
         yrss_fini(c);
@@ -4582,6 +4650,78 @@ int yrss_set_extended(yrss_ctx *c, uint32_t flags)
             return hrc;
     }
     c->ext = flags;   // a launch argument (parse_params): nothing to upload
+    return 0;
+}
+
+int yrss_set_reta(yrss_ctx *c, const uint16_t *table, uint32_t size)
+{
+    if (!c)
+        return -EINVAL;
+    if (!table)
+        size = 0;
+    if (size > YRSS_RETA_MAX || (size & (size - 1u)))   // (0 passes: the table goes)
+        return -EINVAL;
+    for (uint32_t i = 0; i < size; ++i)
+        if (table[i] >= c->cfg.nb_queues)
+            return -EINVAL;
+    if (c->pend.active)   // the burst in flight was queued under the old rule
+        return -EBUSY;
+    if (c->w.on) {
+        // no worker kernel reads a table: the resident launch is halted here
+        // and every start and submit is refused until the table is cleared
+        // (worker_submit); the next submit after that relaunches it
+        if (c->w.pending)
+            return -EBUSY;
+        YRSS_HIP(hipSetDevice(c->device));
+        const int hrc = worker_halt(c);
+        if (hrc)
+            return hrc;
+    }
+    // the device copy first: a failed upload leaves the table in force as it was
+    uint16_t t[YRSS_RETA_MAX] = {};
+    if (size)
+        memcpy(t, table, size * sizeof(uint16_t));
+    YRSS_HIP(hipSetDevice(c->device));
+    YRSS_HIP(hipMemcpy(c->kni.d + kKniWords + kExtWins, t, sizeof(t), hipMemcpyHostToDevice));
+    YRSS_HIP(hipDeviceSynchronize());   // ordered before any stream's next dispatch
+    memcpy(c->reta, t, sizeof(t));
+    c->reta_size = size;
+    return 0;
+}
+
+int yrss_get_reta(yrss_ctx *c, uint16_t *table, uint32_t cap)
+{
+    if (!c || (c->reta_size && (!table || cap < c->reta_size)))
+        return -EINVAL;
+    if (c->reta_size)
+        memcpy(table, c->reta, c->reta_size * sizeof(uint16_t));
+    return (int)c->reta_size;
+}
+
+// Smooth weighted round-robin (include/yrss.h states it step by step).  The
+// running values stay within the sum of the weights either way: 64 bits hold
+// YRSS_MAX_QUEUES weights of 32.
+int yrss_reta_fill_weighted(uint16_t *table, uint32_t size, const uint32_t *weights,
+                            uint32_t nb_queues)
+{
+    if (!table || !weights || size < 1 || size > YRSS_RETA_MAX || (size & (size - 1u)) ||
+        nb_queues < 1 || nb_queues > YRSS_MAX_QUEUES)
+        return -EINVAL;
+    int64_t sum = 0, cur[YRSS_MAX_QUEUES] = {};
+    for (uint32_t k = 0; k < nb_queues; ++k)
+        sum += weights[k];
+    if (!sum)
+        return -EINVAL;
+    for (uint32_t i = 0; i < size; ++i) {
+        uint32_t best = 0;
+        for (uint32_t k = 0; k < nb_queues; ++k) {
+            cur[k] += weights[k];
+            if (cur[k] > cur[best])   // the lowest index on ties
+                best = k;
+        }
+        cur[best] -= sum;
+        table[i] = (uint16_t)best;
+    }
     return 0;
 }
 
@@ -4772,9 +4912,10 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
     P.rbin_chunks = fused ? rcs << lp.gshift : 0u;
     {
         Timed t(c, YRSS_K_PARSE_HASH);
-        hipExtLaunchKernelGGL(pick_parse(ranked ? 2 : compact ? 1 : 0, filter, c->ext != 0u),
+        const bool reta = c->reta_size != 0u, ext = reta || c->ext != 0u;
+        hipExtLaunchKernelGGL(pick_parse(ranked ? 2 : compact ? 1 : 0, filter, ext, reta),
                               dim3(grid), dim3(kParseBlock),
-                              (uint32_t)parse_lds(filter, c->ext != 0u), s, t.a, t.b, 0, P);
+                              (uint32_t)parse_lds(filter, ext, reta), s, t.a, t.b, 0, P);
     }
     YRSS_HIP(hipGetLastError());
     if (fused)
@@ -4948,9 +5089,10 @@ static int dev_seg(yrss_ctx *c, const struct yrss_dev_seg_batch *b, bool route,
     P.seg_off = b->seg_off;
     {
         Timed t(c, YRSS_K_PARSE_HASH);
-        hipExtLaunchKernelGGL(pick_parse(route ? 4 : 3, filter, c->ext != 0u),
+        const bool reta = c->reta_size != 0u, ext = reta || c->ext != 0u;
+        hipExtLaunchKernelGGL(pick_parse(route ? 4 : 3, filter, ext, reta),
                               dim3(grid_for(c, n)), dim3(kParseBlock),
-                              (uint32_t)parse_lds(filter, c->ext != 0u), s, t.a, t.b, 0, P);
+                              (uint32_t)parse_lds(filter, ext, reta), s, t.a, t.b, 0, P);
     }
     YRSS_HIP(hipGetLastError());
     return 0;
@@ -5461,7 +5603,7 @@ int worker_launch(yrss_ctx *c)
     // flags set (an F_EXTENDED worker only: the others are refused before they
     // get here): the kExt kernel and its LDS; flags 0: the plain kernel
     const bool ext = c->ext != 0u;
-    if (ext && !w.ext_ok)
+    if ((ext && !w.ext_ok) || c->reta_size)   // (no worker kernel reads a table)
         return -ENOTSUP;
     if (w.route) {
         if (ext)
@@ -5509,6 +5651,9 @@ int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uin
     // a worker started without YRSS_WORKER_F_EXTENDED serves the reference's
     // rules only, and says so by refusing (yrss_set_extended)
     if (c->ext && !extended)
+        return -ENOTSUP;
+    // no worker follows a redirection table yet (yrss_set_reta)
+    if (c->reta_size)
         return -ENOTSUP;
     if (c->w.on)
         return -EBUSY;
@@ -5608,6 +5753,9 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     // refused, not served by the reference's rules, unless the worker was
     // started to follow the flags (yrss_worker_start_flags)
     if (c->ext && !w.ext_ok)
+        return -ENOTSUP;
+    // nor by hash % d while a redirection table is set (yrss_set_reta)
+    if (c->reta_size)
         return -ENOTSUP;
     if (n > kWorkerMaxBurst)
         return -E2BIG;

@@ -159,6 +159,22 @@ def _flat(a, dtype):
     return None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1)).view(dtype)
 
 
+def reta_weighted(weights, size: int = 128, lib_path: str | None = None):
+    """A redirection table of ``size`` entries over the queues
+    ``0..len(weights) - 1`` in proportion to ``weights`` (smooth weighted
+    round-robin, ``yrss_reta_fill_weighted``; pure host code).  Weight 0 keeps
+    a queue out; equal weights give ``table[i] == i % len(weights)``."""
+    w = np.asarray(weights)
+    if w.ndim != 1 or np.any(w < 0) or np.any(w > 0xFFFFFFFF):
+        raise ValueError("weights are a flat list of 32-bit unsigned numbers")
+    w = np.ascontiguousarray(w, dtype=np.uint32)
+    t = np.zeros(max(int(size), 1), np.uint16)
+    abi.check(abi.load(lib_path).yrss_reta_fill_weighted(t.ctypes.data, int(size), w.ctypes.data,
+                                                          int(w.size)),
+              "yrss_reta_fill_weighted")
+    return t
+
+
 class SoftRss:
     """One engine context on one GPU (``yrss_ctx``)."""
 
@@ -266,6 +282,33 @@ class SoftRss:
             (abi.EXT_UDP if udp else 0)
         abi.check(self._lib.yrss_set_extended(self._ctx, flags), "yrss_set_extended")
         self.ext_flags = flags
+
+    # -- redirection table (this build's own semantics as well) --------------
+    def set_reta(self, table=None) -> None:
+        """Queue of a hashed packet from a redirection table
+        (``yrss_set_reta``): ``table[hash & (len(table) - 1)]`` in place of
+        ``hash % d (+1)``; a power of two of entries, 1..``abi.RETA_MAX``, each
+        below ``nb_queues``.  ``None`` (or an empty table) restores the
+        reference's rule exactly.  Unhashed and truncated packets keep their
+        queues.  The persistent worker does not follow a table: its starts and
+        submits are refused (ENOTSUP) while one is set."""
+        if table is None or len(table) == 0:
+            rc = self._lib.yrss_set_reta(self._ctx, None, 0)
+        else:
+            t = np.asarray(table)
+            if t.ndim != 1 or np.any(t < 0) or np.any(t > 0xFFFF):
+                raise ValueError("a redirection table is a flat list of queue ids")
+            t = np.ascontiguousarray(t, dtype=np.uint16)
+            rc = self._lib.yrss_set_reta(self._ctx, t.ctypes.data, int(t.size))
+        abi.check(rc, "yrss_set_reta")
+
+    def get_reta(self):
+        """The table in force (uint16 array), ``None`` when none is set
+        (``yrss_get_reta``)."""
+        t = np.zeros(abi.RETA_MAX, np.uint16)
+        size = self._lib.yrss_get_reta(self._ctx, t.ctypes.data, abi.RETA_MAX)
+        abi.check(size, "yrss_get_reta")
+        return t[:size].copy() if size else None
 
     # -- device-resident path ---------------------------------------------
     def dispatch_dev(self, win, lens, stride: int, n: int | None = None, *,

@@ -3706,6 +3706,21 @@ uint32_t resident_blocks(yrss_ctx *c, const void *fn, uint32_t block, uint32_t l
     return blocks;
 }
 
+// The rule a launch classifies under, as the kernels' template parameters kExt
+// and kReta.  A table launch uses the kExt kernels whatever the flags (with
+// P.ext == 0 ext_classify is the reference's rule), so (false, true) does not
+// occur.  (For the one-launch kernel and the worker; the grid launches still
+// take bare booleans)
+struct RuleVariant {
+    bool ext, reta;
+};
+
+RuleVariant rule_variant(const yrss_ctx *c)
+{
+    const bool reta = c->reta_size != 0u;
+    return {reta || c->ext != 0u, reta};
+}
+
 typedef void (*ParseKernel)(ParseParams);
 
 // count: 0 none, 1 per-chunk counts, 2 counts + per-packet chunk ranks,
@@ -3969,6 +3984,26 @@ void host_reg_poison(void *base)
 int worker_halt(yrss_ctx *c);
 void worker_free(yrss_ctx *c);
 
+// Before yrss_set_extended or yrss_set_reta changes the rule a started
+// worker's launch carries: -EBUSY while a worker burst is pending, else the
+// launch is halted (worker_halt's code).  (yrss_set_kni has the same block for
+// a route worker, without these callers' c->pend.active test in front.)
+int quiesce_worker_for_rule_change(yrss_ctx *c)
+{
+    if (c->w.pending)
+        return -EBUSY;
+    YRSS_HIP(hipSetDevice(c->device));
+    return worker_halt(c);
+}
+
+// Whether a worker serves the rule in force, 0 or -ENOTSUP: one started
+// without YRSS_WORKER_F_EXTENDED (ext_ok false) refuses while flags are set,
+// and no worker kernel reads a redirection table.
+int worker_serves_rule(const yrss_ctx *c, bool ext_ok)
+{
+    return (c->ext && !ext_ok) || c->reta_size ? -ENOTSUP : 0;
+}
+
 uint64_t mono_ns()
 {
     timespec ts;
@@ -4065,6 +4100,29 @@ SmallParams small_params(const yrss_ctx *c, int route_lq = -1)
     return S;
 }
 
+typedef void (*SmallKernel)(SmallParams);
+
+// The one-launch kernel for a form under a rule.  (Route in an if of its own:
+// the kernels' order in the code object follows their first naming, which is
+// to stay the launches' order, and a nested ?: names its inner arms first.)
+SmallKernel pick_small(bool filter, bool route, RuleVariant v)
+{
+    if (v.reta) {
+        if (route)
+            return yrss_burst_small<true, true, true, true>;
+        return filter ? yrss_burst_small<true, false, true, true>
+                      : yrss_burst_small<false, false, true, true>;
+    }
+    if (v.ext) {
+        if (route)
+            return yrss_burst_small<true, true, true>;
+        return filter ? yrss_burst_small<true, false, true> : yrss_burst_small<false, false, true>;
+    }
+    if (route)
+        return yrss_burst_small<true, true>;
+    return filter ? yrss_burst_small<true> : yrss_burst_small<false>;
+}
+
 // One launch of yrss_burst_small, S from small_params with the caller's
 // windows and output pointers (route: S.qidx / S.qstart the routed lists).
 // host_burst: a host-resident burst on the context stream, completed by the
@@ -4081,35 +4139,9 @@ int small_launch(yrss_ctx *c, SmallParams &S, bool filter, bool host_burst = tru
     } else {
         S.done = nullptr;
     }
-    const bool reta = c->reta_size != 0u;   // (S.P.mod_d is then the table's size)
-    const size_t lds = small_lds(S.P.nb, filter || route, reta || S.P.ext != 0u, reta);
-    const dim3 grid(1);
-    if (reta) {
-        if (route)
-            hipLaunchKernelGGL((yrss_burst_small<true, true, true, true>), grid,
-                               dim3(kSmallBlock), lds, stream, S);
-        else if (filter)
-            hipLaunchKernelGGL((yrss_burst_small<true, false, true, true>), grid,
-                               dim3(kSmallBlock), lds, stream, S);
-        else
-            hipLaunchKernelGGL((yrss_burst_small<false, false, true, true>), grid,
-                               dim3(kSmallBlock), lds, stream, S);
-    } else if (S.P.ext) {
-        if (route)
-            hipLaunchKernelGGL((yrss_burst_small<true, true, true>), grid, dim3(kSmallBlock), lds,
-                               stream, S);
-        else if (filter)
-            hipLaunchKernelGGL((yrss_burst_small<true, false, true>), grid, dim3(kSmallBlock),
-                               lds, stream, S);
-        else
-            hipLaunchKernelGGL((yrss_burst_small<false, false, true>), grid, dim3(kSmallBlock),
-                               lds, stream, S);
-    } else if (route)
-        hipLaunchKernelGGL((yrss_burst_small<true, true>), grid, dim3(kSmallBlock), lds, stream, S);
-    else if (filter)
-        hipLaunchKernelGGL(yrss_burst_small<true>, grid, dim3(kSmallBlock), lds, stream, S);
-    else
-        hipLaunchKernelGGL(yrss_burst_small<false>, grid, dim3(kSmallBlock), lds, stream, S);
+    const RuleVariant v = rule_variant(c);   // (under a table S.P.mod_d is its size)
+    hipLaunchKernelGGL(pick_small(filter, route, v), dim3(1), dim3(kSmallBlock),
+                       small_lds(S.P.nb, filter || route, v.ext, v.reta), stream, S);
     YRSS_HIP(hipGetLastError());
     return 0;
 }
@@ -4642,12 +4674,8 @@ int yrss_set_extended(yrss_ctx *c, uint32_t flags)
         // YRSS_WORKER_F_EXTENDED is relaunched under the new flags by its next
         // submit; any other serves the reference's rules only and refuses
         // submits while flags are set
-        if (c->w.pending)
-            return -EBUSY;
-        YRSS_HIP(hipSetDevice(c->device));
-        const int hrc = worker_halt(c);
-        if (hrc)
-            return hrc;
+        if (const int rc = quiesce_worker_for_rule_change(c))
+            return rc;
     }
     c->ext = flags;   // a launch argument (parse_params): nothing to upload
     return 0;
@@ -4670,12 +4698,8 @@ int yrss_set_reta(yrss_ctx *c, const uint16_t *table, uint32_t size)
         // no worker kernel reads a table: the resident launch is halted here
         // and every start and submit is refused until the table is cleared
         // (worker_submit); the next submit after that relaunches it
-        if (c->w.pending)
-            return -EBUSY;
-        YRSS_HIP(hipSetDevice(c->device));
-        const int hrc = worker_halt(c);
-        if (hrc)
-            return hrc;
+        if (const int rc = quiesce_worker_for_rule_change(c))
+            return rc;
     }
     // the device copy first: a failed upload leaves the table in force as it was
     uint16_t t[YRSS_RETA_MAX] = {};
@@ -5571,6 +5595,17 @@ int worker_halt(yrss_ctx *c)
     return e == hipSuccess ? 0 : hip_fail("worker halt", e);
 }
 
+typedef void (*WorkerKernel)(WorkerParams);
+
+// The worker kernel for a rule: the kExt one under flags, which only an
+// F_EXTENDED worker gets to (worker_serves_rule).  No worker kernel has kReta.
+WorkerKernel pick_worker(bool route, RuleVariant v)
+{
+    if (route)
+        return v.ext ? yrss_burst_worker<true, true> : yrss_burst_worker<true>;
+    return v.ext ? yrss_burst_worker<false, true> : yrss_burst_worker<false>;
+}
+
 int worker_launch(yrss_ctx *c)
 {
     auto &w = c->w;
@@ -5600,26 +5635,11 @@ int worker_launch(yrss_ctx *c)
     W.idle_ticks = w.idle_ticks;
     W.life_ticks = w.life_ticks;
     W.poll_sleep = w.poll_sleep;
-    // flags set (an F_EXTENDED worker only: the others are refused before they
-    // get here): the kExt kernel and its LDS; flags 0: the plain kernel
-    const bool ext = c->ext != 0u;
-    if ((ext && !w.ext_ok) || c->reta_size)   // (no worker kernel reads a table)
-        return -ENOTSUP;
-    if (w.route) {
-        if (ext)
-            hipLaunchKernelGGL((yrss_burst_worker<true, true>), dim3(w.nblocks),
-                               dim3(kSmallBlock), worker_lds(w.nbk, true, true), w.stream, W);
-        else
-            hipLaunchKernelGGL(yrss_burst_worker<true>, dim3(w.nblocks), dim3(kSmallBlock),
-                               worker_lds(w.nbk, true), w.stream, W);
-    } else {
-        if (ext)
-            hipLaunchKernelGGL((yrss_burst_worker<false, true>), dim3(w.nblocks),
-                               dim3(kSmallBlock), worker_lds(c->nb, false, true), w.stream, W);
-        else
-            hipLaunchKernelGGL(yrss_burst_worker<false>, dim3(w.nblocks), dim3(kSmallBlock),
-                               worker_lds(c->nb), w.stream, W);
-    }
+    if (const int rc = worker_serves_rule(c, w.ext_ok))
+        return rc;
+    const RuleVariant v = rule_variant(c);   // (v.reta was refused just above)
+    hipLaunchKernelGGL(pick_worker(w.route, v), dim3(w.nblocks), dim3(kSmallBlock),
+                       worker_lds(w.nbk, w.route, v.ext), w.stream, W);
     YRSS_HIP(hipGetLastError());
     w.running = true;
     return 0;
@@ -5648,13 +5668,8 @@ int worker_start(yrss_ctx *c, uint32_t nslots, uint32_t nblocks, bool route, uin
         return -EINVAL;
     if (route && c->cfg.nb_queues > YRSS_ROUTE_LISTS_MAX_QUEUES)
         return -ENOTSUP;
-    // a worker started without YRSS_WORKER_F_EXTENDED serves the reference's
-    // rules only, and says so by refusing (yrss_set_extended)
-    if (c->ext && !extended)
-        return -ENOTSUP;
-    // no worker follows a redirection table yet (yrss_set_reta)
-    if (c->reta_size)
-        return -ENOTSUP;
+    if (const int rc = worker_serves_rule(c, extended))
+        return rc;
     if (c->w.on)
         return -EBUSY;
     YRSS_HIP(hipSetDevice(c->device));
@@ -5750,13 +5765,8 @@ int worker_submit(yrss_ctx *c, const void *ptrs, const uint16_t *lens, uint32_t 
     auto &w = c->w;
     if (!w.on)
         return -ENODEV;
-    // refused, not served by the reference's rules, unless the worker was
-    // started to follow the flags (yrss_worker_start_flags)
-    if (c->ext && !w.ext_ok)
-        return -ENOTSUP;
-    // nor by hash % d while a redirection table is set (yrss_set_reta)
-    if (c->reta_size)
-        return -ENOTSUP;
+    if (const int rc = worker_serves_rule(c, w.ext_ok))
+        return rc;
     if (n > kWorkerMaxBurst)
         return -E2BIG;
     const uint64_t t = w.issued + 1u;

@@ -998,6 +998,7 @@ __global__ __launch_bounds__(kBlock) void yrss_parse_hash(ParseParams P)
         // -6 us in one run and +3 us in another (profiles/r04_flush_policy_ab.log,
         // r04_early_flush_ab.log)
         static_assert(kBlock % kWaves == 0, "a thread keeps its wave");
+        static_assert(8 % kWaves == 0, "a round's kWaves columns lie in one scatter range");
         // With tot_acc the workgroup also sums its counts per bucket (in the
         // staging LDS, free after the loop) and adds them to the batch totals,
         // so the line scatter needs no scan kernel in front of it
@@ -1718,6 +1719,19 @@ __global__ __launch_bounds__(kLineBlock, kG == 4u ? 2 : 4) void yrss_scatter_lin
     extern __shared__ __attribute__((aligned(16))) uint32_t lsm[];
     const uint32_t nb = P.nb, t = threadIdx.x, lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(t / kWave);
+    if (P.fused) {
+        // the next batch's totals and range bins start from zero (no one
+        // reads them in this kernel; each workgroup clears a slice), also
+        // where this kernel leaves at its capacity check: the next batch
+        // adds onto that set whatever became of this one
+        const uint32_t G = gridDim.x;
+        if (blockIdx.x == 0 && t < nb)
+            P.tot_next[t] = 0u;
+        const uint32_t zw = kLbMaxWgs * nb, per = (zw + G - 1u) / G;
+        for (uint32_t e = blockIdx.x * per + t; e < min(zw, (blockIdx.x + 1u) * per);
+             e += kLineBlock)
+            P.rbin_next[e] = 0u;
+    }
     // Capacity, checked before any barrier (the condition is uniform): a
     // plan past what this instantiation holds reports and leaves, instead of
     // running on unwritten per-bucket words (see line_nb_max)
@@ -1747,15 +1761,6 @@ __global__ __launch_bounds__(kLineBlock, kG == 4u ? 2 : 4) void yrss_scatter_lin
     const uint32_t r = P.fused ? blockIdx.x : xcd_block(P.xcd), G = gridDim.x;
     const uint32_t g0 = P.fused ? min(r * P.rcs, nsp) : (uint32_t)((uint64_t)r * nsp / G);
     const uint32_t g1 = P.fused ? min(g0 + P.rcs, nsp) : (uint32_t)((uint64_t)(r + 1u) * nsp / G);
-    if (P.fused) {
-        // the next batch's totals and range bins start from zero (no one
-        // reads them in this kernel; each workgroup clears a slice)
-        if (blockIdx.x == 0 && t < nb)
-            P.tot_next[t] = 0u;
-        const uint32_t zw = kLbMaxWgs * nb, per = (zw + G - 1u) / G;
-        for (uint32_t e = r * per + t; e < min(zw, (r + 1u) * per); e += kLineBlock)
-            P.rbin_next[e] = 0u;
-    }
     // prefix table rows are ncs + 1 words apart: with a power-of-two row the
     // lanes of one chunk column hit one or two LDS banks whatever their bucket
     // (a 0.78 conflict share of the LDS cycles at 64 buckets)
@@ -4904,7 +4909,9 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
             const uint32_t g_eff = (spans + rcs_ - 1) / rcs_;
             const uint32_t rc = rcs_ << lp.gshift;
             const uint32_t lds = line_lds(c->nb, lp.gshift, lp.lmax, rc + 1u).words * 4u;
-            if (rc % 8u == 0 && rc <= kFusedMaxCols && g_eff <= kFusedMaxRanges &&
+            // (rc a multiple of the parse workgroup's waves: a round's columns
+            // lie in one range, which the parse kernel's range bins rest on)
+            if (rc % (kParseBlock / kWave) == 0 && rc <= kFusedMaxCols && g_eff <= kFusedMaxRanges &&
                 c->nb <= kFusedRows * (kLineBlock / kWave - 1u) && lds <= 160u * 1024u &&
                 resident_blocks(c, (const void *)line_fn, kLineBlock, lds) >= g_eff) {
                 fused = true;
@@ -4942,8 +4949,6 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
                               (uint32_t)parse_lds(filter, ext, reta), s, t.a, t.b, 0, P);
     }
     YRSS_HIP(hipGetLastError());
-    if (fused)
-        W.tot_set = tset ^ 1u;   // this batch's scatter zeroes it for the next
     if (!compact)
         return 0;
     if (!fused) {
@@ -5004,6 +5009,21 @@ int dispatch_dev_impl(yrss_ctx *c, const struct yrss_dev_batch *b, void *stream)
         Timed t(c, YRSS_K_SCATTER);
         hipExtLaunchKernelGGL(line_fn, dim3(line_grid), dim3(kLineBlock), line_lds_bytes, s, t.a,
                               t.b, 0, S);
+        if (fused) {
+            // The next batch takes the other set, which this scatter zeroes,
+            // only once the scatter is queued.  Where it is not, the parse
+            // kernel's sums stay in this set with no scatter to clear the
+            // other: this set is cleared here and used again.
+            const hipError_t le = hipGetLastError();
+            if (le != hipSuccess) {
+                (void)hipMemsetAsync(W.tot_acc.d + (size_t)tset * c->nb, 0,
+                                     c->nb * sizeof(uint32_t), s);
+                (void)hipMemsetAsync(W.rbin.d + (size_t)tset * kLbMaxWgs * c->nb, 0,
+                                     (size_t)kLbMaxWgs * c->nb * sizeof(uint32_t), s);
+                YRSS_HIP(le);
+            }
+            W.tot_set = tset ^ 1u;
+        }
         YRSS_HIP(hipGetLastError());
         return 0;
     }
